@@ -2,7 +2,9 @@
 """Headline benchmark: embeddings/sec on 2 s @ 16 kHz synthetic utterances through a speaker model
 (wav -> Kaldi fbank -> CMN -> forward, all in the HIP library) + PLDA trials/sec.
 
-    python bench.py [--gpus N --steps K --warmup W] [--model M] [--precision P]
+    python bench.py [--gpus N --steps K --warmup W] [--model M] [--precision P]      # the headline figure alone
+    python bench.py --full [...]                         # + everything else this file measures (below)
+    python bench.py [...] --dump-outputs DIR             # + the last timed step's arrays as DIR/<name>.npy
     python bench.py --gpus 8 --workload vox1o            # fixed-size set, strong scaling
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -23,9 +25,15 @@ Two workload shapes:
 
 Which number is the headline.  The reference path north_star names is PyTorch **fp32**; the parity-grade back-end is
 WS_PREC_FP32 (exact fp32 products on v_mfma_f32_32x32x2_f32) and `value` / `dtype` / `roofline` describe THAT run
-(`--precision fp32`, the default).  f16x3 and f16 are declared fast modes, timed on the same workload in the same
-process and reported under `backends`, each with its own `roofline` block (dominant kernel class measured live with
-HIP events on the launch stream).
+(`--precision fp32`, the default).  With `--full`, f16x3 and f16 -- the declared fast modes -- are timed on the same
+workload in the same process and reported under `backends`, each with its own `roofline` block (dominant kernel class
+measured live with HIP events on the launch stream).
+
+Plain run and `--full`.  A plain run sets up, runs W warm-up steps, times ONE region of exactly K steps (`value`,
+`ms_per_step`), writes `--dump-outputs` if asked and prints the line.  Everything else -- further timed windows
+(median / spread), the one-batch-in-flight windows and the per-class event pass behind `roofline`, the self-check
+against a small-batch run, the other back-ends, the other BASELINE configs and fixed-size sets, the PLDA leg and the
+CPU baselines -- runs only with `--full`, which `--headline-only`, `--no-configs` and `--no-cpu-baseline` narrow.
 
 What goes where.  Rank 0 prints ONE compact JSON line (< 8 KB; `compact_line`: the contract's keys, the headline
 `roofline` and `cpu_baseline`, `plda`, one figure per other BASELINE config, the fixed-size sets) and writes the full
@@ -591,6 +599,24 @@ def emit(full, detail_path):
     print(compact_line(full, name), flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dump_dir, tensors):
+    """--dump-outputs: the arrays the last timed step returned, one `<name>.npy` each (float32 stays float32, anything
+    else becomes float64).  All of them together stay under DUMP_LIMIT_BYTES: an array over its share is cut to a
+    fixed, seeded sample of its rows (the same rows in every run, in ascending order)."""
+    os.makedirs(dump_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(tensors)) - 4096          # (.npy header)
+    for key, t in tensors.items():
+        a = t.detach().cpu().numpy()
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        if a.nbytes > share:
+            keep = max(1, share // max(1, a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.RandomState(20240607).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(dump_dir, key + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------ main
 def parse_args(argv):
     ap = argparse.ArgumentParser()
@@ -611,9 +637,17 @@ def parse_args(argv):
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--trials", type=int, default=1000000)
     ap.add_argument("--cpu-utts", type=int, default=1500)
-    ap.add_argument("--windows", type=int, default=5,
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: more timed windows, the "
+                         "roofline passes, the self-check, the other back-ends and BASELINE configs, the PLDA leg, "
+                         "the CPU baselines (a plain run only warms up, times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned to DIR/<name>.npy (float32 / "
+                         "float64): `embeddings`, and in the fixed-size set mode rank 0's `llr` and `cosine` scores")
+    ap.add_argument("--windows", type=int, default=None,
                     help="timed windows of --steps steps per back-end (the first one of the headline back-end "
-                         "is the contract's timed region = `value`; all of them give median / spread)")
+                         "is the contract's timed region = `value`; all of them give median / spread); "
+                         "default: 1, with --full 5")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--plda-only", action="store_true",
                     help="only the PLDA leg (for rocprofv3: the kernel table then holds the plda_* kernels alone)")
@@ -638,7 +672,12 @@ def parse_args(argv):
     ap.add_argument("--precision", default="fp32", choices=list(BACKENDS),
                     help="back-end of the headline (`value`): fp32 = the reference's arithmetic (default); "
                          "f16x3 / f16 are the declared fast modes, always reported under `backends`")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
+    if args.dump_outputs and args.plda_only:
+        ap.error("--dump-outputs describes the embedding path; --plda-only has no such step")
+    return args
 
 
 def main(argv=None):
@@ -728,7 +767,7 @@ def main(argv=None):
 
     # ======================================================================= fixed-size set (strong scaling)
     def run_set(model_name, embed_dim, n_utts, n_trials, prec, steps, warmup, per_batch, per_chunk, model=None,
-                lanes_obj=None):
+                lanes_obj=None, dump_dir=None):
         """U utterances cut into contiguous shards (parallel.shard_range), every rank walks its shard in batches,
         one all_gather, rank 0 scores `n_trials` (PLDA LLR + cosine).  One step = the whole set."""
         lo, hi = parallel.shard_range(n_utts, rank, world)
@@ -820,10 +859,16 @@ def main(argv=None):
             # order-sensitive: row i weighted by i + 1 (a gather that permuted the shards keeps the plain checksum)
             wts = torch.arange(1, n_utts + 1, dtype=torch.float64, device=emb.device)
             res["embedding_order_checksum"] = float((emb.double().abs().sum(1) * wts).sum().item())
+            if dump_dir:
+                arrays = {"embeddings": emb}
+                if sc is not None:
+                    arrays["llr"], arrays["cosine"] = sc
+                dump_outputs(dump_dir, arrays)
         return res, m
 
     if set_mode:
-        res, _ = run_set(name, E, total_utts, set_trials, args.precision, args.steps, args.warmup, batch, chunk)
+        res, _ = run_set(name, E, total_utts, set_trials, args.precision, args.steps, args.warmup, batch, chunk,
+                         dump_dir=args.dump_outputs)
         if rank == 0:
             line = {
                 "metric": METRIC, "value": res["value"], "unit": "embeddings/s", "n_gpus": world,
@@ -895,8 +940,10 @@ def main(argv=None):
         """EXACTLY `steps` steps between two fences; max over ranks; HIP events bracket only the dominant
         kernel class inside it (events around all ~45 launches per chunk cost ~12 %)."""
         fence()
-        events = not STUB and not use_lanes[0]      # with several batches in flight the kernels of the lanes share
-        if events:                                  # the CUs: a launch's begin -> end is not its own duration
+        # with several batches in flight the kernels of the lanes share the CUs: a launch's begin -> end is not its
+        # own duration (and only --full reads the events)
+        events = args.full and not STUB and not use_lanes[0]
+        if events:
             model.profile(1)
         t0 = time.perf_counter()
         for _ in range(steps):
@@ -985,6 +1032,10 @@ def main(argv=None):
                  "windows_embeddings_per_s": [round(v, 1) for v in vals],
                  "median": statistics.median(vals), "min": min(vals), "max": max(vals),
                  "spread_rel": (max(vals) - min(vals)) / statistics.median(vals)}
+        if args.dump_outputs and out is not None:
+            out = out.clone()           # the last timed step's rows, before any later pass reuses their buffer
+        if not args.full:
+            return block, out
         if lanes_here:
             # the same steps on ONE lane (every launch behind the previous one): the per-kernel durations of the
             # roofline block come from these windows -- with several batches in flight the lanes' kernels overlap
@@ -1024,6 +1075,9 @@ def main(argv=None):
     # ---- headline back-end first: W warmup steps, then the contract's timed region (window 0)
     blocks = {}
     blocks[args.precision], all_emb = run_backend(args.precision, args.steps, args.warmup, max(1, args.windows))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"embeddings": all_emb})
+    extras = args.full and not args.headline_only and not STUB      # the legs beside the headline back-end
 
     # ---- sustained window: the contract's region is K steps (80 ms at the default K); the same
     # step function held for --sustain-s seconds in ONE timed region, with the shader clock sampled every 10 ms by a
@@ -1086,7 +1140,7 @@ def main(argv=None):
 
     # ---- rows of the TIMED output against a small-batch run of the same utterances (the timed kernels did the work)
     self_check = None
-    if rank == 0 and not STUB:
+    if rank == 0 and args.full and not STUB:
         rows = sorted({0, 1, batch // 2, batch - 1})
         small = model.extract(fe, wav[rows])
         big = all_emb[rows].to(small.device)
@@ -1098,7 +1152,7 @@ def main(argv=None):
                               "moves the fp32 summation order of the SE / context statistics)" % len(rows)}
         assert self_check["ok"], self_check
 
-    if not args.headline_only and not STUB:
+    if extras:
         for other in [m for m in BACKENDS if m != args.precision]:
             blocks[other], _ = run_backend(other, max(3, min(args.steps, 10)), 2, max(1, min(args.windows, 3)))
     model.set_precision(args.precision)
@@ -1109,8 +1163,7 @@ def main(argv=None):
     # ---- the other BASELINE.json configs, compact: per model one fp32 leg with its dominant-class fraction (HIP
     # events) + the f16 rate; and the two fixed-size sets (configs 2 / 3) at this N
     configs = None
-    if rank == 0 and world == 1 and not args.headline_only and not args.no_configs and not STUB \
-            and name == "ECAPA_TDNN_GLOB_c512":
+    if rank == 0 and world == 1 and extras and not args.no_configs and name == "ECAPA_TDNN_GLOB_c512":
         configs = {}
         keep = {}
         for cname in ("ECAPA_TDNN_GLOB_c1024", "ResNet34", "ResNet221", "CAMPPlus"):
@@ -1184,7 +1237,7 @@ def main(argv=None):
     # ---- the same workload at larger per-GPU batches (fp32 headline back-end): what the fixed per-launch costs (~45
     # launches, the latency-bound SE / pooling kernels, the partial last rounds of tiles) take at batch 256
     batch_sweep = None
-    if rank == 0 and world == 1 and not args.headline_only and not STUB and not args.batch and args.batch_sweep:
+    if rank == 0 and world == 1 and extras and not args.batch and args.batch_sweep:
         batch_sweep = {}
         for b in (512, 1024):
             bm = make_model(name, E, b, T)
@@ -1226,7 +1279,7 @@ def main(argv=None):
 
     # ---- PLDA leg (rank 0 scores after the gather; 1 M synthetic trial pairs over 10 k embeddings)
     plda_info = None
-    if rank == 0 and not args.headline_only and not STUB:
+    if rank == 0 and extras:
         plda_info = plda_leg(args, device, world == 1 and not args.no_cpu_baseline)
 
     if rank == 0:
@@ -1272,7 +1325,7 @@ def main(argv=None):
         line["embedding_checksum"] = float(all_emb.double().abs().sum().item())
         line["collective_backend"] = dist.get_backend() if active else None
         line["collective"] = collective_info()
-        if world == 1 and not args.no_cpu_baseline and not args.headline_only and not STUB:
+        if world == 1 and not args.no_cpu_baseline and extras:
             heavy = name.startswith("ResNet") and name not in ("ResNet18", "ResNet34")
             line["cpu_baseline"] = cpu_baseline(name, E, args.cpu_utts, budget_s=6.0 if heavy else 8.0)
         assert all_emb.shape == (n_total, E) and bool(torch.isfinite(all_emb).all())

@@ -142,6 +142,61 @@ def test_stub_lines_are_short_and_the_detail_file_is_written(tmp_path):
         assert full["value"] == pytest.approx(line["value"], rel=1e-5)
 
 
+def test_dump_outputs_writes_the_last_step_and_repeats_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: the arrays the last timed step returned as DIR/<name>.npy (float32 / float64); the same
+    arguments give the same inputs, hence the same files, in a second process; --steps is the number of timed steps
+    and the line carries ms_per_step."""
+    import numpy as np
+    for mode, argv, names in (
+            ("default", ("--gpus", "1", "--batch", "8", "--steps", "2", "--warmup", "1"), {"embeddings": (8, 192)}),
+            ("set", ("--gpus", "2", "--total-utts", "37", "--set-trials", "50", "--batch", "8", "--steps", "2",
+                     "--warmup", "1"), {"embeddings": (37, 192), "llr": (50,), "cosine": (50,)})):
+        runs = []
+        for k in range(2):
+            d = tmp_path / ("%s_%d" % (mode, k))
+            line = run_bench(*argv, "--dump-outputs", str(d))
+            assert line["steps"] == 2 and line["ms_per_step"] > 0
+            assert line["value"] == pytest.approx(line["config"].get("global_batch", 37) / (line["ms_per_step"] * 1e-3),
+                                                  rel=1e-3)
+            assert sorted(os.listdir(str(d))) == sorted(n + ".npy" for n in names)
+            runs.append({n: np.load(str(d / (n + ".npy"))) for n in names})
+        for n, shape in names.items():
+            a, b = runs[0][n], runs[1][n]
+            assert a.shape == shape and a.dtype in (np.float32, np.float64) and np.isfinite(a).all()
+            assert np.array_equal(a, b), n
+        assert runs[0]["embeddings"].dtype == np.float32 and np.abs(runs[0]["embeddings"]).max() > 0
+
+
+def test_dump_outputs_samples_rows_of_an_array_over_its_share(tmp_path, monkeypatch):
+    """An output over its share of the size limit is cut to a fixed, seeded, ascending sample of its rows."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * (4096 + 10 * 64 * 4))
+    big = torch.arange(100 * 64, dtype=torch.float32).reshape(100, 64)
+    small = torch.arange(5, dtype=torch.int32)
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / str(k)), {"big": big, "small": small})
+    a, b = np.load(str(tmp_path / "0" / "big.npy")), np.load(str(tmp_path / "1" / "big.npy"))
+    assert a.shape == (10, 64) and a.dtype == np.float32 and np.array_equal(a, b)
+    rows = (a[:, 0] / 64).astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, big.numpy()[rows])
+    s = np.load(str(tmp_path / "0" / "small.npy"))
+    assert s.dtype == np.float64 and np.array_equal(s, np.arange(5))
+    total = sum(os.path.getsize(str(tmp_path / "0" / f)) for f in os.listdir(str(tmp_path / "0")))
+    assert total <= bench.DUMP_LIMIT_BYTES
+
+
+def test_plain_run_has_one_window_and_full_has_five():
+    """A plain run times one region of --steps steps; the further windows (median / spread) belong to --full."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"]).windows == 1
+    assert bench.parse_args(["--full"]).windows == 5 and not bench.parse_args([]).full
+    assert bench.parse_args(["--windows", "3"]).windows == 3
+
+
 def test_eight_ranks_value_is_priced_on_the_slowest_rank_and_scoring_is_inside_the_step():
     """What the driver's 8-GPU node will rely on, with the host stand-in on gloo at world size 8:
     (a) `value` = all ranks' utterances / the MAX-over-ranks time -- rank 5 is made 1 s slower per extract call, rank 0

@@ -1438,7 +1438,7 @@ def test_bench_two_ranks_with_lanes_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, WS_SHARE_GPU="1", WS_DIST_BACKEND="gloo", PYTHONPATH=root)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-                        "--windows", "1", "--batch", "64", "--headline-only"], env=env, cwd=root,
+                        "--windows", "1", "--batch", "64", "--full", "--headline-only"], env=env, cwd=root,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -28,7 +28,7 @@ def main():
                 for kv in v.split(","):
                     k, val = kv.split("=")
                     env[k] = val
-            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--headline-only", "--windows", "3", "--sustain-s", "0"]
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--headline-only", "--windows", "3", "--sustain-s", "0"]
             cmd += shlex.split(args.bench_args)
             out = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
             try:

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 i=0
 for c in "$@"; do
   i=$((i+1)); rm -rf /tmp/pmc_$i
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d /tmp/pmc_$i -- python "$REPO/bench.py" $ARGS --steps 2 --warmup 1 --windows 1 --headline-only --lanes 1 > /tmp/pmc_$i.log 2>&1 || tail -3 /tmp/pmc_$i.log
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d /tmp/pmc_$i -- python "$REPO/bench.py" $ARGS --steps 2 --warmup 1 --windows 1 --full --headline-only --lanes 1 > /tmp/pmc_$i.log 2>&1 || tail -3 /tmp/pmc_$i.log
 done
 python - "$NEEDLE" /tmp/pmc_* <<'PY'
 import sys, csv, glob, os, collections

@@ -18,14 +18,14 @@ fi
 if want bench; then
 # the driver's line (default: ECAPA-512, fp32 headline + both fast modes + config 1 + PLDA + cpu baseline)
 # (the driver's command line; stdout = the compact line, bench_detail.json = the full record)
-python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/${TAG}_bench_n1.json" 2> "$OUT/${TAG}_bench_n1.err"; cut -c1-200 "$OUT/${TAG}_bench_n1.json"; wc -c "$OUT/${TAG}_bench_n1.json"
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/${TAG}_bench_n1.json" 2> "$OUT/${TAG}_bench_n1.err"; cut -c1-200 "$OUT/${TAG}_bench_n1.json"; wc -c "$OUT/${TAG}_bench_n1.json"
 cp bench_detail.json "$OUT/${TAG}_bench_detail.json" 2>/dev/null
 fi
 if want models; then
 # the other families of BASELINE.json (configs 2-3) through the same bench.py
 rm -f "$OUT/${TAG}_bench_models.jsonl" "$OUT/${TAG}_bench_sets.jsonl"
 for m in ECAPA_TDNN_GLOB_c1024 ResNet34 ResNet221 CAMPPlus; do
-  python bench.py --model $m --steps 10 --windows 3 --cpu-utts 300 --no-configs 2> /dev/null | tail -1 >> "$OUT/${TAG}_bench_models.jsonl"
+  python bench.py --full --model $m --steps 10 --windows 3 --cpu-utts 300 --no-configs 2> /dev/null | tail -1 >> "$OUT/${TAG}_bench_models.jsonl"
 done
 # BASELINE configs 2 / 3 as fixed-size sets (strong scaling; at N = 1 here, `--gpus N` on a multi-GPU node)
 python bench.py --workload vox1o --steps 3 --warmup 1 2> /dev/null | tail -1 >> "$OUT/${TAG}_bench_sets.jsonl"
@@ -50,7 +50,7 @@ prof() {  # name, bench args...
   if [ -n "$PROFS" ]; then case " $PROFS " in *" $name "*) ;; *) return 0;; esac; fi
   rm -rf "$OUT/prof_$name"
   # --lanes 1: every launch behind the previous one, so that a kernel's begin -> end in the table is its own duration
-  local base="--headline-only --steps 20 --windows 1 --lanes 1 --sustain-s 0"
+  local base="--full --headline-only --steps 20 --windows 1 --lanes 1 --sustain-s 0"
   [ "$name" = plda ] && base=""
   rocprofv3 --kernel-trace --stats -d "$OUT/prof_$name" -o p -- python "$REPO/bench.py" $base "$@" > "$OUT/prof_$name.log" 2>&1
   python "$REPO/tools/rocprof_summary.py" "$(ls $OUT/prof_$name/*.db 2>/dev/null | head -1)" > "$OUT/${TAG}_kernel_stats_$name.md" 2>/dev/null
@@ -77,7 +77,7 @@ pmc() {  # prec, needle, [model]
   for c in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
     i=$((i+1))
     rm -rf "$OUT/pmc_${prec}_$i"
-    rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$OUT/pmc_${prec}_$i" -- python "$REPO/bench.py" --model $model --precision $prec --steps 3 --warmup 1 --windows 1 --headline-only --lanes 1 > /dev/null 2>&1
+    rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$OUT/pmc_${prec}_$i" -- python "$REPO/bench.py" --model $model --precision $prec --steps 3 --warmup 1 --windows 1 --full --headline-only --lanes 1 > /dev/null 2>&1
   done
   python "$REPO/tools/pmc_traffic.py" $prec "$needle" "$OUT/pmc_${prec}_1" "$OUT/pmc_${prec}_2" "$OUT/pmc_${prec}_3" > "$OUT/${TAG}_pmc_dominant_kernel_$prec$tag.json"
   grep -E "traffic_bytes_per_launch|mfma_busy|\"traffic_bytes\"" "$OUT/${TAG}_pmc_dominant_kernel_$prec$tag.json"
