@@ -112,6 +112,19 @@ def synth_ecapa_state_dict(model_name="ECAPA_TDNN_GLOB_c512", feat_dim=80, embed
     return g.sd
 
 
+def cancelling_channel_state_dict(seed=7, c=5):
+    """An ECAPA-GLOB weight set in which channel `c` of h = ReLU(conv(cat)) sits at ~200 with a spread of a few 1e-2
+    (|mean| / std ~ 1e3..1e4), its context STD drives the attention strongly, and its pooled output std (which the
+    reference itself computes by the cancelling form, pooling_layers.py:141-143) is kept out of the embedding."""
+    sd = synth_ecapa_state_dict("ECAPA_TDNN_GLOB_c512", 80, 192, seed=seed)
+    sd = {k: np.array(v, copy=True) for k, v in sd.items()}
+    sd["conv.weight"][c] *= 1e-3
+    sd["conv.bias"][c] = 200.0
+    sd["pool.linear1.weight"][:, 3072 + c, 0] = 3.0 * np.sign(sd["pool.linear1.weight"][:, 3072 + c, 0] + 1e-9)
+    sd["linear.weight"][:, 1536 + c] = 0.0
+    return sd
+
+
 RESNET_LAYOUTS = {      # reference resnet.py:207-260: (bottleneck, blocks per stage)
     "ResNet18": (False, [2, 2, 2, 2]), "ResNet34": (False, [3, 4, 6, 3]),
     "ResNet50": (True, [3, 4, 6, 3]), "ResNet101": (True, [3, 4, 23, 3]),

@@ -61,9 +61,9 @@ typedef void* ws_stream;                /* hipStream_t */
 /* ------------------------------------------------------------------------------------ misc */
 /* Bumped whenever an exported signature changes (101: ws_plda_stats takes `emb_is_f64` and a void* table since
  * round 2 -- a caller built against 100 would pass shifted arguments; 104: ws_frontend_set_cmvn / ws_cmvn added, the
- * `cmn` flags now mean "apply the frontend's CMVN"; 105: ws_forward_ragged_cmvn added).  ws_version() returns the library's value:
- * compare it with the header's before calling anything else. */
-#define WS_VERSION 105
+ * `cmn` flags now mean "apply the frontend's CMVN"; 105: ws_forward_ragged_cmvn added; 106: ws_debug_engine_tap added).
+ * ws_version() returns the library's value: compare it with the header's before calling anything else. */
+#define WS_VERSION 106
 WS_API int ws_version(void);
 WS_API const char* ws_last_error(void);
 /* Number of fbank frames for num_samples at snip_edges=True (25 ms / 10 ms):
@@ -274,6 +274,23 @@ WS_API int ws_debug_clock_probe(uint64_t* out, int samples, int64_t period_ticks
  * outputs are the specialised kernel's bits, which is how the tests pin it.  Returns 0, or WS_ERR_INVALID_ARG for an
  * unknown mode. */
 WS_API int ws_debug_fbank_mode(int mode);
+/* Read-only tap on the activations a forward leaves in the engine's workspace (no reference counterpart; the per-layer
+ * parity tests of tests/test_gpu_layers.py).  A stream-ordered device-to-device copy of the named fp32 tensor as the
+ * LAST chunk of the LAST forward on this engine left it (a batch beyond max_batch runs in chunks: the tap holds the
+ * utterances of the last one).  ECAPA-TDNN names, workspace layout, channels contiguous:
+ *   frame level, rows = B * T_slot:  out1 (C)  cat = out2 | out3 | out4 (3C)  h (1536)
+ *                                    y1, y2, y3 (C): conv1 / Res2 / conv3 output of the last block (layer4), before SE
+ *   utterance level, rows = B:       se_s (C, layer4's gate)  stats = [mean; std] (3072, GLOB models)
+ *                                    bias_img (128, GLOB models)  pooled (3072)
+ * Rows beyond an utterance's own frames (ragged forward) are the zeros the kernels stored there.
+ * dst DEVICE float32[cap_floats], or NULL to ask for the shape only; rows / cols (HOST, may be NULL) receive it.
+ * WS_ERR_INVALID_ARG (message in ws_last_error): unknown name; a tensor the last forward did not leave in fp32
+ * (WS_PREC_F16 with T >= 64 keeps the block chain and h in binary16 only; stats / bias_img exist for GLOB models);
+ * a model family without taps (ResNet, CAM++); no forward since the engine was finalized / its workspace re-sized.
+ * WS_ERR_CAPACITY: cap_floats < rows * cols.  The forward path itself is unchanged: a few host-side integers remember
+ * the last chunk. */
+WS_API int ws_debug_engine_tap(ws_engine* eng, const char* name, float* dst, int64_t cap_floats, int32_t* rows,
+                               int32_t* cols, ws_stream stream);
 /* Algorithmic FLOPs (2 x MACs of every conv/linear) of one forward at (batch, num_frames). */
 WS_API double ws_engine_flops(const ws_engine* eng, int batch, int num_frames);
 

@@ -226,17 +226,7 @@ def test_ecapa_forward_matches_oracle_and_golden(name, golden_dir):
     assert _rel_err(got_s, g[name + "/emb_T57"]).max() < REL_TOL
 
 
-def _cancelling_channel_fixture(seed=7, c=5):
-    """An ECAPA-GLOB weight set in which channel `c` of h = ReLU(conv(cat)) sits at ~200 with a spread of a few 1e-2
-    (|mean| / std ~ 1e3..1e4), its context STD drives the attention strongly, and its pooled output std (which the
-    reference itself computes by the cancelling form, pooling_layers.py:141-143) is kept out of the embedding."""
-    sd = synth.synth_ecapa_state_dict("ECAPA_TDNN_GLOB_c512", 80, 192, seed=seed)
-    sd = {k: np.array(v, copy=True) for k, v in sd.items()}
-    sd["conv.weight"][c] *= 1e-3
-    sd["conv.bias"][c] = 200.0
-    sd["pool.linear1.weight"][:, 3072 + c, 0] = 3.0 * np.sign(sd["pool.linear1.weight"][:, 3072 + c, 0] + 1e-9)
-    sd["linear.weight"][:, 1536 + c] = 0.0
-    return sd
+_cancelling_channel_fixture = synth.cancelling_channel_state_dict      # (shared with tests/test_gpu_layers.py)
 
 
 def test_ecapa_glob_context_std_two_pass_fallback():

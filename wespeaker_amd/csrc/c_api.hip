@@ -714,6 +714,17 @@ int ws_debug_fbank_mode(int mode) {
   return WS_OK;
 }
 
+int ws_debug_engine_tap(ws_engine* eng, const char* name, float* dst, int64_t cap_floats, int32_t* rows, int32_t* cols,
+                        ws_stream stream) {
+  if (!eng || !name || cap_floats < 0) { set_error("ws_debug_engine_tap: invalid argument"); return WS_ERR_INVALID_ARG; }
+  if (!eng->finalized) {
+    set_error("ws_debug_engine_tap: no forward has run on this engine (it is not finalized)");
+    return WS_ERR_INVALID_ARG;
+  }
+  WS_HIP_CHECK(hipSetDevice(eng->device));
+  return eng->model->tap(name, dst, cap_floats, rows, cols, (hipStream_t)stream);
+}
+
 long long ws_debug_dispatch_report(char* buf, long long cap) {
   if (cap < 0 || (cap > 0 && !buf)) { set_error("ws_debug_dispatch_report: invalid argument"); return WS_ERR_INVALID_ARG; }
   return (long long)dispatch_log_dump(buf, (size_t)cap);

@@ -204,6 +204,13 @@ struct Model {
   // Engine-internal invariants that a kernel bug could break silently (ws_engine_check_range calls it behind its
   // stream synchronisation): 0, or a WS_ERR_* with the message set.  ResNet: the zero pads behind its activation buffers.
   virtual int check_invariants() { return 0; }
+  // ws_debug_engine_tap: copy the named fp32 workspace tensor of the last forward chunk to dst (device; null = shape
+  // only).  Families without taps keep this default.
+  virtual int tap(const char* name, float* dst, int64_t cap_floats, int32_t* rows, int32_t* cols, hipStream_t stream) {
+    (void)dst; (void)cap_floats; (void)rows; (void)cols; (void)stream;
+    set_error("ws_debug_engine_tap: this model family has no activation taps (tensor '%s'; ECAPA-TDNN only)", name);
+    return WS_ERR_INVALID_ARG;
+  }
   virtual int set_precision(int mode) = 0;   // 0 exact fp32 MFMA, 1 split-f16 x3 MFMA
   virtual float* feats_workspace() = 0;      // (max_batch, max_frames, feat_dim) floats
   virtual int max_batch() const = 0;

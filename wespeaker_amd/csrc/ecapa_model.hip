@@ -111,6 +111,7 @@ struct EcapaModel : ModelBase {
   int reserve(int max_batch, int max_frames) override {
     int err = 0;
     maxB = max_batch; maxT = max_frames;
+    last_chunk = LastChunk();                  // the taps address the old layout
     const size_t M = (size_t)maxB * maxT;
     size_t total = 0;
     auto take = [&](size_t n) { size_t o = total; total += (n + 63) & ~size_t(63); return o; };
@@ -148,6 +149,7 @@ struct EcapaModel : ModelBase {
     // ... and with T >= 64 (SE statistics from the epilogue) the block chain out1 -> y3 -> cat lives in
     // binary16 only: the residual stream is rounded once per block like in any fp16 inference engine
     const bool allf16 = f16io && T >= 64;
+    last_chunk.B = 0;                          // (taps: nothing to read until this chunk has been enqueued in full)
     {
       ConvGemmParams p0 = conv1d(layer1, feats, feat_dim, 0, out1, C, 0, B, T, 1, ACT_RELU);
       if (f16io) { p0.D16 = out1_16; p0.ldd16 = C; }
@@ -339,7 +341,36 @@ struct EcapaModel : ModelBase {
     // BN + Linear (+bn2), folded: split-K GEMM over K = 3072
     WS_LAUNCH(gemm_splitk(conv1d(final_lin, pooled, 3072, 0, emb, embed_dim, 0, B, 1, 1, ACT_NONE),
                           partial, kSplitK, st));
+    last_chunk.B = B; last_chunk.T = T; last_chunk.prec = gemm_precision;
+    last_chunk.chain_half = allf16;
+    last_chunk.y2_half = f16io && res2_half_out_supported(w, T, 4);
     return 0;
+  }
+
+  // ws_debug_engine_tap: the fp32 tensors forward_chunk leaves behind (layout: reserve(); [rows][cols] contiguous)
+  int tap(const char* name, float* dst, int64_t cap_floats, int32_t* rows, int32_t* cols, hipStream_t st) override {
+    const LastChunk& lc = last_chunk;
+    if (lc.B <= 0) {
+      set_error("ws_debug_engine_tap: no forward has run on this engine since it was finalized / re-sized");
+      return WS_ERR_INVALID_ARG;
+    }
+    const int M = lc.B * lc.T;
+    const char* half = "the f16 back-end with T >= 64 keeps it in binary16 only";
+    const char* noglob = "only the GLOB models compute the context statistics";
+    const std::string n = name;
+    if (n == "out1") return tap_copy(name, lc.chain_half ? nullptr : out1, half, M, C, dst, cap_floats, rows, cols, st);
+    if (n == "cat") return tap_copy(name, lc.chain_half ? nullptr : cat, half, M, 3 * C, dst, cap_floats, rows, cols, st);
+    if (n == "h") return tap_copy(name, lc.chain_half ? nullptr : h, half, M, 1536, dst, cap_floats, rows, cols, st);
+    if (n == "y1") return tap_copy(name, y1, "", M, C, dst, cap_floats, rows, cols, st);
+    if (n == "y2") return tap_copy(name, lc.y2_half ? nullptr : y2, "the f16 back-end's fused Res2 chain stores binary16 only",
+                                   M, C, dst, cap_floats, rows, cols, st);
+    if (n == "y3") return tap_copy(name, lc.chain_half ? nullptr : y3, half, M, C, dst, cap_floats, rows, cols, st);
+    if (n == "se_s") return tap_copy(name, se_s, "", lc.B, C, dst, cap_floats, rows, cols, st);
+    if (n == "stats") return tap_copy(name, glob ? stats : nullptr, noglob, lc.B, 3072, dst, cap_floats, rows, cols, st);
+    if (n == "bias_img") return tap_copy(name, glob ? bias_img : nullptr, noglob, lc.B, 128, dst, cap_floats, rows, cols, st);
+    if (n == "pooled") return tap_copy(name, pooled, "", lc.B, 3072, dst, cap_floats, rows, cols, st);
+    set_error("ws_debug_engine_tap: unknown tensor '%s' (out1, cat, h, y1, y2, y3, se_s, stats, bias_img, pooled)", name);
+    return WS_ERR_INVALID_ARG;
   }
 
   double flops(int batch, int T) const override {

@@ -82,6 +82,33 @@ struct ModelBase : Model {
   virtual int forward_chunk(const float* feats, int B, int T, float* emb, hipStream_t st) = 0;
   virtual int min_frames() const = 0;
 
+  // ---- activation taps (ws_debug_engine_tap): what the last forward chunk left in the workspace.  Host-side
+  // integers only; B = 0 until a chunk has run to its end (and again after the workspace was re-laid-out).
+  struct LastChunk {
+    int B = 0, T = 0, prec = 0;
+    bool chain_half = false;     // out1 / cat / y3 / h exist as binary16 only
+    bool y2_half = false;        // the last block's Res2 output exists as binary16 only
+  } last_chunk;
+  // one entry of a family's tap table: rows x cols fp32, contiguous at src (null: not produced in fp32)
+  int tap_copy(const char* name, const float* src, const char* why_absent, int rows_n, int cols_n, float* dst,
+               int64_t cap_floats, int32_t* rows, int32_t* cols, hipStream_t st) {
+    if (!src) {
+      set_error("ws_debug_engine_tap: the last forward left no fp32 '%s' (%s)", name, why_absent);
+      return WS_ERR_INVALID_ARG;
+    }
+    if (rows) *rows = rows_n;
+    if (cols) *cols = cols_n;
+    if (!dst) return WS_OK;
+    const int64_t n = (int64_t)rows_n * cols_n;
+    if (cap_floats < n) {
+      set_error("ws_debug_engine_tap: '%s' is %d x %d floats, the destination holds %lld", name, rows_n, cols_n,
+                (long long)cap_floats);
+      return WS_ERR_CAPACITY;
+    }
+    WS_HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return WS_OK;
+  }
+
   const int* upload_lens(const int32_t* lens_host, int batch, int frames, hipStream_t st) override {
     if ((size_t)batch > lens_cap) {
       if (hipStreamSynchronize(st) != hipSuccess) return nullptr;

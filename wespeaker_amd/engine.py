@@ -243,6 +243,30 @@ class NativeSpeakerModel:
                 _lib.check(_lib.lib().ws_engine_check_range(self._h, _lib.current_stream_ptr(self.device)),
                            "ws_engine_check_range")
 
+    TAP_NAMES = ("out1", "cat", "h", "y1", "y2", "y3", "se_s", "stats", "bias_img", "pooled")
+
+    def tap_shape(self, name):
+        """(rows, cols) of a tap without copying it (ws_debug_engine_tap with a NULL destination)."""
+        rows, cols = ctypes.c_int32(0), ctypes.c_int32(0)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().ws_debug_engine_tap(self._h, name.encode(), None, 0, ctypes.byref(rows),
+                                                      ctypes.byref(cols), _lib.current_stream_ptr(self.device)),
+                       "ws_debug_engine_tap(%s)" % name)
+        return rows.value, cols.value
+
+    def tap(self, name) -> torch.Tensor:
+        """Diagnostic: a copy of the fp32 activation `name` (TAP_NAMES; ECAPA-TDNN) that the last chunk of the last
+        forward left in the engine's workspace, as a (rows, cols) tensor on the GPU -- rows = B * T_slot for the
+        frame-level tensors, B for se_s / stats / bias_img / pooled; channels contiguous (ws_debug_engine_tap).
+        Raises NativeError for a tensor that forward did not leave in fp32."""
+        rows, cols = self.tap_shape(name)
+        out = torch.empty((rows, cols), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().ws_debug_engine_tap(self._h, name.encode(), _lib.ptr(out), out.numel(), None, None,
+                                                      _lib.current_stream_ptr(self.device)),
+                       "ws_debug_engine_tap(%s)" % name)
+        return out
+
     def flops(self, batch, frames) -> float:
         return float(_lib.lib().ws_engine_flops(self._h, int(batch), int(frames)))
 
