@@ -171,6 +171,41 @@ def synth_resnet_state_dict(model_name="ResNet34", feat_dim=80, embed_dim=256,
     return g.sd
 
 
+SIMAM_RESNET_LAYOUTS = {      # reference samresnet.py:126-131: blocks per stage
+    "SimAM_ResNet34_ASP": [3, 4, 6, 3], "SimAM_ResNet100_ASP": [6, 16, 24, 3],
+}
+
+
+def synth_simam_resnet_state_dict(model_name="SimAM_ResNet34_ASP", feat_dim=80, embed_dim=256, in_planes=64, seed=42):
+    """SimAM_ResNet34_ASP / SimAM_ResNet100_ASP (samresnet.py:134-167): `front` = the SimAM BasicBlock ResNet of
+    width in_planes, `pooling` = ASP (pooling_layers.py:151-186), `bottleneck` = Linear."""
+    blocks = SIMAM_RESNET_LAYOUTS[model_name]
+    m = int(in_planes)
+    g = _Init(seed)
+    g.conv("front.conv1", m, 1, 3, 3, bias=False)
+    g.bn("front.bn1", m)
+    cin = m
+    for s, nb in enumerate(blocks):
+        planes = m * (2 ** s)
+        for b in range(nb):
+            stride = (1 if s == 0 else 2) if b == 0 else 1
+            p = "front.layer%d.%d" % (s + 1, b)
+            g.conv(p + ".conv1", planes, cin, 3, 3, bias=False)
+            g.bn(p + ".bn1", planes)
+            g.conv(p + ".conv2", planes, planes, 3, 3, bias=False, gain=0.25)
+            g.bn(p + ".bn2", planes)
+            if stride != 1 or cin != planes:
+                g.conv(p + ".downsample.0", planes, cin, 1, 1, bias=False, gain=1.0)
+                g.bn(p + ".downsample.1", planes)
+            cin = planes
+    d = m * 8 * (feat_dim // 8)
+    g.conv("pooling.attention.0", 128, d, 1, gain=1.0)
+    g.bn("pooling.attention.2", 128)
+    g.conv("pooling.attention.3", d, 128, 1, gain=8.0)      # wide logits -> non-trivial softmax
+    g.linear("bottleneck", embed_dim, 2 * d)
+    return g.sd
+
+
 def synth_campplus_state_dict(feat_dim=80, embed_dim=512, seed=42):
     g = _Init(seed)
     g.conv("head.conv1", 32, 1, 3, 3, bias=False)
@@ -213,6 +248,10 @@ def synth_campplus_state_dict(feat_dim=80, embed_dim=512, seed=42):
 
 
 def synth_state_dict(model_name, feat_dim=80, embed_dim=None, seed=42, **kw):
+    if model_name.startswith("SimAM_ResNet"):
+        kw.pop("pooling_func", None)
+        return synth_simam_resnet_state_dict(model_name, feat_dim, embed_dim or 256,
+                                             in_planes=kw.pop("in_planes", 64), seed=seed)
     if model_name.startswith("ECAPA_TDNN"):
         kw.pop("pooling_func", None)
         return synth_ecapa_state_dict(model_name, feat_dim, embed_dim or 192, seed=seed, **kw)
@@ -235,8 +274,12 @@ def write_model_dir(model_dir, model_name, feat_dim=80, embed_dim=192, seed=42, 
     sd = synth_state_dict(model_name, feat_dim, embed_dim, seed=seed, **model_kw)
     torch.save(OrderedDict((k, torch.from_numpy(np.asarray(v))) for k, v in sd.items()),
                os.path.join(model_dir, "avg_model.pt"))
-    model_args = dict(feat_dim=feat_dim, embed_dim=embed_dim)
-    model_args["pooling_func"] = "ASTP" if model_name.startswith("ECAPA") else "TSTP"
+    if model_name.startswith("SimAM_ResNet"):
+        # the reference constructor's own arguments (samresnet.py:135): no feat_dim, no pooling_func
+        model_args = dict(in_planes=model_kw.pop("in_planes", 64), embed_dim=embed_dim, acoustic_dim=feat_dim, dropout=0)
+    else:
+        model_args = dict(feat_dim=feat_dim, embed_dim=embed_dim)
+        model_args["pooling_func"] = "ASTP" if model_name.startswith("ECAPA") else "TSTP"
     model_args.update(model_kw)
     cfg = {
         "model": model_name,

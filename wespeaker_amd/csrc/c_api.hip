@@ -262,6 +262,7 @@ int ws_engine_create(const char* model_name, int feat_dim, int embed_dim, int de
   Model* m = make_ecapa(model_name, feat_dim, embed_dim);
   if (!m) m = make_resnet(model_name, feat_dim, embed_dim);
   if (!m) m = make_campplus(model_name, feat_dim, embed_dim);
+  if (!m) m = make_samresnet(model_name, feat_dim, embed_dim);
   if (!m) {
     set_error("ws_engine_create: unknown model '%s'", model_name);
     return WS_ERR_UNKNOWN_MODEL;
@@ -657,8 +658,10 @@ int ws_extract_windows(ws_engine* eng, ws_frontend* fe, const void* wav, int wav
 
 int ws_engine_set_precision(ws_engine* eng, int mode) {
   if (!eng) { set_error("ws_engine_set_precision: invalid argument"); return WS_ERR_INVALID_ARG; }
+  set_error("");
   int r = eng->model->set_precision(mode);
-  if (r) set_error("ws_engine_set_precision: unknown mode %d (0 = fp32 MFMA, 1 = split-f16 x3, 2 = f16)", mode);
+  // (a family that refuses a valid mode says why itself: SimAM-ResNet and mode 2)
+  if (r && !*get_error()) set_error("ws_engine_set_precision: unknown mode %d (0 = fp32 MFMA, 1 = split-f16 x3, 2 = f16)", mode);
   return r;
 }
 

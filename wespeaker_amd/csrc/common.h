@@ -220,6 +220,7 @@ struct Model {
 Model* make_ecapa(const std::string& model_name, int feat_dim, int embed_dim);
 Model* make_resnet(const std::string& model_name, int feat_dim, int embed_dim);
 Model* make_campplus(const std::string& model_name, int feat_dim, int embed_dim);
+Model* make_samresnet(const std::string& model_name, int feat_dim, int embed_dim);
 
 }  // namespace wsamd
 

@@ -260,6 +260,23 @@ hipError_t launch_tstp(const float* x, int ldx, int B, int F, int T, int C, cons
 hipError_t launch_tstp_f16(const uint16_t* x16, int ldx, int B, int F, int T, int C,
                            const float* pre_scale, const float* pre_shift, float* pooled,
                            hipStream_t stream, const int* lens = nullptr);
+// ---- SimAM-ResNet (simam_ops.hip)
+// the stem for any channel count C % 4 == 0 (fp32 only): same semantics as launch_stem_conv3x3
+hipError_t launch_stem_conv3x3_any(const float* feats, int B, int T, int F, const float* w, const float* b, int C,
+                                   float* out, hipStream_t stream, const int* lens = nullptr);
+// SimAM gate + residual + ReLU (samresnet.py:57-70) over channels-last y[(b*F + f)*T + t][C] (conv2 + bn2, no
+// activation): per (utterance, channel) plane statistics over the F x lens[b] valid pixels,
+//   out = relu(y * sigmoid((y - mu)^2 / (4 (v + 1e-4)) + 0.5) + res),  v = sum (y - mu)^2 / (F * len - 1);
+// columns t >= lens[b] are left out of the statistics and stored as zeros.  out may be y.  16 <= C <= 1024, C % 4 == 0.
+// Three launches (slice partials, merge, apply); scratch: part B * simam_slices(F*T, C) * 3 * C floats, mu / kk B * C.
+int simam_slices(int rows, int C);
+hipError_t launch_simam_residual_relu(const float* y, const float* res, int ldr, float* out, int B, int F, int T,
+                                      int C, const int* lens, float* part, float* mu, float* kk,
+                                      hipStream_t stream);
+// ASP (pooling_layers.py:188-204): softmax over the valid t of the logits e[(b*T + t)][f*C + c], weighted mean / std
+// (variance clamped at 1e-5) of x[(b*F + f)*T + t][c] -> pooled[b] = [mean(D) | std(D)], D index c*F + f
+hipError_t launch_asp_pool(const float* x, const float* e, int B, int F, int T, int C, float* pooled,
+                           hipStream_t stream, const int* lens = nullptr);
 // CAM++ context (campplus.py:108-135): ctx = mean_T(h) + segmean_100(h); m = sigmoid(W2 relu(W1 ctx + b1) + b2)
 // h: [B*T][C] (C = 128); mask out: [B][segs][Cout]
 hipError_t launch_cam_context_from_colsum(const float* colsum, int B, int T, int C, const float* w1,

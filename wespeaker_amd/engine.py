@@ -20,9 +20,29 @@ WINDOW_TYPES = {"hamming": 0, "povey": 1}
 
 SUPPORTED_MODELS = ("ECAPA_TDNN_c512", "ECAPA_TDNN_GLOB_c512", "ECAPA_TDNN_c1024",
                     "ECAPA_TDNN_GLOB_c1024", "ResNet18", "ResNet34", "ResNet50", "ResNet101",
-                    "ResNet152", "ResNet221", "ResNet293", "CAMPPlus")
+                    "ResNet152", "ResNet221", "ResNet293", "CAMPPlus", "SimAM_ResNet34_ASP", "SimAM_ResNet100_ASP")
 
-DEFAULT_EMBED_DIM = {"ECAPA": 192, "ResNe": 256, "CAMPP": 512}
+DEFAULT_EMBED_DIM = {"ECAPA": 192, "ResNe": 256, "CAMPP": 512, "SimAM": 256}
+
+
+def simam_model_args(state_dict, feat_dim, model_args):
+    """The constructor arguments of SimAM_ResNet34_ASP / SimAM_ResNet100_ASP (samresnet.py:135: in_planes, embed_dim,
+    acoustic_dim, dropout) in this package's terms -> (feat_dim, remaining model_args).  acoustic_dim is the feature
+    dimension; in_planes is what the engine reads from the checkpoint, so a config that disagrees with it raises
+    ValueError; dropout is an eval no-op.  A `pooling_func` key is dropped by the callers before this point: the
+    reference constructor has no such argument (it would raise TypeError), the pooling of this family is always ASP,
+    and configs written by generic tooling carry the key -- so it is ignored rather than refused."""
+    model_args = dict(model_args)
+    acoustic_dim = model_args.pop("acoustic_dim", None)
+    if acoustic_dim is not None:
+        feat_dim = int(acoustic_dim)
+    model_args.pop("dropout", None)
+    in_planes = model_args.pop("in_planes", None)
+    w = state_dict.get("front.conv1.weight") if hasattr(state_dict, "get") else None
+    if in_planes is not None and w is not None and int(w.shape[0]) != int(in_planes):
+        raise ValueError("in_planes=%d in the model arguments, but front.conv1.weight of the checkpoint has %d "
+                         "output channels" % (int(in_planes), int(w.shape[0])))
+    return feat_dim, model_args
 
 
 def default_device() -> torch.device:
@@ -179,6 +199,8 @@ class NativeSpeakerModel:
 
     def __init__(self, model_name: str, state_dict, feat_dim=80, embed_dim=None, device=None,
                  max_batch=64, max_frames=400, **unused_model_args):
+        if model_name.startswith("SimAM_ResNet"):
+            feat_dim, unused_model_args = simam_model_args(state_dict, feat_dim, unused_model_args)
         self.device = torch.device(device) if device is not None else default_device()
         self.model_name = model_name
         self.feat_dim = int(feat_dim)
@@ -244,6 +266,7 @@ class NativeSpeakerModel:
                            "ws_engine_check_range")
 
     TAP_NAMES = ("out1", "cat", "h", "y1", "y2", "y3", "se_s", "stats", "bias_img", "pooled")
+    SIMAM_TAP_NAMES = ("block1", "pooled")    # SimAM_ResNet*_ASP: first block's output (B*F*T, in_planes), ASP vector
 
     def tap_shape(self, name):
         """(rows, cols) of a tap without copying it (ws_debug_engine_tap with a NULL destination)."""
@@ -329,10 +352,11 @@ class NativeSpeakerModel:
     def __call__(self, feats: torch.Tensor):
         """Return convention of the reference modules (callers use `outputs[-1] if tuple`):
         ECAPA -> (out4, embed) (ecapa_tdnn.py:227-234), ResNet -> (tensor(0.0), embed_a) or
-        (embed_a, embed_b) (resnet.py:192-204), CAM++ -> tensor (campplus.py:409-413).
-        The leading element is not materialised on this path (None for ECAPA / two-layer ResNet)."""
+        (embed_a, embed_b) (resnet.py:192-204), CAM++ -> tensor (campplus.py:409-413), SimAM_ResNet*_ASP -> tensor
+        (samresnet.py:142-149).  The leading element is not materialised on this path (None for ECAPA / two-layer
+        ResNet)."""
         emb = self.embed(feats)
-        if self.model_name.startswith("CAMPPlus"):
+        if self.model_name.startswith(("CAMPPlus", "SimAM_ResNet")):
             return emb
         if self.model_name.startswith("ResNet"):
             return torch.tensor(0.0), emb

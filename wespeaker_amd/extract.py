@@ -759,6 +759,9 @@ def build_gpu_extractor(configs, model_path, device=None, max_batch=256, max_fra
     feat_dim = int(margs.pop("feat_dim", fc["num_mel_bins"]))
     embed_dim = margs.pop("embed_dim", None)
     sd = _load_state_dict(model_path)
+    if configs["model"].startswith("SimAM_ResNet"):      # in_planes / acoustic_dim / dropout (engine.simam_model_args)
+        from .engine import simam_model_args
+        feat_dim, margs = simam_model_args(sd, feat_dim, margs)
     if lanes <= 0:
         lanes = 2
     if lanes > 1:
