@@ -61,9 +61,10 @@ typedef void* ws_stream;                /* hipStream_t */
 /* ------------------------------------------------------------------------------------ misc */
 /* Bumped whenever an exported signature changes (101: ws_plda_stats takes `emb_is_f64` and a void* table since
  * round 2 -- a caller built against 100 would pass shifted arguments; 104: ws_frontend_set_cmvn / ws_cmvn added, the
- * `cmn` flags now mean "apply the frontend's CMVN"; 105: ws_forward_ragged_cmvn added; 106: ws_debug_engine_tap added).
+ * `cmn` flags now mean "apply the frontend's CMVN"; 105: ws_forward_ragged_cmvn added; 106: ws_debug_engine_tap added;
+ * 107: ws_debug_engine_stop_after added).
  * ws_version() returns the library's value: compare it with the header's before calling anything else. */
-#define WS_VERSION 106
+#define WS_VERSION 107
 WS_API int ws_version(void);
 WS_API const char* ws_last_error(void);
 /* Number of fbank frames for num_samples at snip_edges=True (25 ms / 10 ms):
@@ -282,15 +283,37 @@ WS_API int ws_debug_fbank_mode(int mode);
  *                                    y1, y2, y3 (C): conv1 / Res2 / conv3 output of the last block (layer4), before SE
  *   utterance level, rows = B:       se_s (C, layer4's gate)  stats = [mean; std] (3072, GLOB models)
  *                                    bias_img (128, GLOB models)  pooled (3072)
+ * ResNet names (tests/test_gpu_resnet_layers.py), maps in the layout [b][f][t][c] as rows = B * H * W, cols = C.  The
+ * model rotates four activation buffers, so only the LAST EXECUTED block's tensors survive a forward: set a stop point
+ * (ws_debug_engine_stop_after) to read an earlier block.
+ *   stem     the stem's output (32)                        -- only when stopped at 0
+ *   block    the last executed block's output
+ *   mid      its BasicBlock conv1 / Bottleneck conv2 output (planes)
+ *   sc       its shortcut convolution's output             -- only when the block has one
+ *   next_y1  the NEXT block's conv1 output                 -- only when the fused conv3 + conv1 kernel ran for the block
+ *   pooled (B, 2 * stats_dim)   emb_a (B, E; two-embedding models: seg_1's output after its relu + seg_bn_1 epilogue,
+ *   what seg_2 reads)                                      -- only after a full forward
+ * SimAM-ResNet names: block (the gated result), mid (conv1's output), sc (the downsample convolution's output), and
+ * after a full forward hid (B * T', 128: the first attention layer), logits (B * T', D; D in f * C + c order),
+ * pooled (B, 2D); block1 = a copy of the first block's output made during the forward.
  * Rows beyond an utterance's own frames (ragged forward) are the zeros the kernels stored there.
  * dst DEVICE float32[cap_floats], or NULL to ask for the shape only; rows / cols (HOST, may be NULL) receive it.
  * WS_ERR_INVALID_ARG (message in ws_last_error): unknown name; a tensor the last forward did not leave in fp32
- * (WS_PREC_F16 with T >= 64 keeps the block chain and h in binary16 only; stats / bias_img exist for GLOB models);
- * a model family without taps (ResNet, CAM++); no forward since the engine was finalized / its workspace re-sized.
+ * (WS_PREC_F16 with T >= 64 keeps the block chain and h in binary16 only, and every ResNet map; stats / bias_img exist
+ * for GLOB models; a block without a shortcut has no sc, an unfused one no next_y1, a stopped forward no pooled);
+ * a model family without taps (CAM++); no forward since the engine was finalized / its workspace re-sized.
  * WS_ERR_CAPACITY: cap_floats < rows * cols.  The forward path itself is unchanged: a few host-side integers remember
  * the last chunk. */
 WS_API int ws_debug_engine_tap(ws_engine* eng, const char* name, float* dst, int64_t cap_floats, int32_t* rows,
                                int32_t* cols, ws_stream stream);
+/* Debug stop point of the 2-D families (ResNet, SimAM-ResNet; no reference counterpart): every later forward on this
+ * engine returns after the stem (n_blocks = 0) or after the last launch of the n-th residual block (a fused
+ * conv3 + next-conv1 launch belongs to block n), so that ws_debug_engine_tap can read what those launches left.
+ * Pooling and the head do not run; the embedding output is zero-filled on the stream.  -1 (the default) = the full
+ * forward: with it no launch, store or dispatch decision differs from a library without the stop point (one host-side
+ * integer, tested once per block).  WS_ERR_INVALID_ARG: n_blocks < -1 or beyond the model's block count; a family
+ * without a block loop (ECAPA-TDNN, CAM++); an engine that is not finalized. */
+WS_API int ws_debug_engine_stop_after(ws_engine* eng, int n_blocks);
 /* Algorithmic FLOPs (2 x MACs of every conv/linear) of one forward at (batch, num_frames). */
 WS_API double ws_engine_flops(const ws_engine* eng, int batch, int num_frames);
 

@@ -37,21 +37,28 @@ def simam(x, lambda_p=LAMBDA):
     return x * torch.sigmoid(d / (4 * (v + lambda_p)) + 0.5)
 
 
-def _block(sd, p, x, stride, mid=None):
+def _block(sd, p, x, stride, mid=None, taps=None):
     out = F.relu(_conv_bn(sd, p + ".conv1", p + ".bn1", x, stride=stride, padding=1))
     y = _conv_bn(sd, p + ".conv2", p + ".bn2", out, padding=1)
     sc = x
     if p + ".downsample.0.weight" in sd:
         sc = _conv_bn(sd, p + ".downsample.0", p + ".downsample.1", x, stride=stride)
+        if taps is not None:
+            taps["sc"] = sc
     if mid is not None:
         mid["block1_y"], mid["block1_res"] = y, sc
-    return F.relu(simam(y) + sc)
+    res = F.relu(simam(y) + sc)
+    if taps is not None:
+        taps["mid"], taps["block"] = out, res
+    return res
 
 
 def asp(sd, x, mid=None):
     """x (B, C, F, T) -> (B, 2 C F)."""
     x = x.reshape(x.size(0), -1, x.size(-1))
     h = F.relu(F.conv1d(x, _t(sd, "pooling.attention.0.weight"), _t(sd, "pooling.attention.0.bias")))
+    if mid is not None:
+        mid["hid"] = h
     h = _bn(sd, "pooling.attention.2", h)
     e = F.conv1d(h, _t(sd, "pooling.attention.3.weight"), _t(sd, "pooling.attention.3.bias"))
     w = torch.softmax(e, dim=2)
@@ -67,17 +74,23 @@ def simam_resnet_forward(sd, feats, model_name="SimAM_ResNet34_ASP", return_inte
     """feats (B, T, F) -> embedding (B, E) in `dtype` (float64: the ground truth; float32: what a faithful fp32
     implementation computes).  return_intermediates: also a dict with `block1` (the first block's output, (B, C, F, T)),
     `block1_y` / `block1_res` (what its SimAM gate and residual add read: conv2 + bn2, and the block input), `pooled`
-    (the ASP vector, (B, 2D)) and `logits` (the attention logits, (B, D, T'))."""
+    (the ASP vector, (B, 2D)), `logits` (the attention logits, (B, D, T')), `hid` (the first attention layer after its
+    ReLU, before the BatchNorm1d, (B, 128, T')), `stem` (B, C, F, T) and, for the i-th residual block (1-based), `b<i>.mid`
+    (conv1 + bn1 + relu), `b<i>.block` (the gated result), `b<i>.sc` where the block has a downsample convolution."""
     blocks = LAYOUTS[model_name]
     sd = _cast(sd, dtype)
     x = torch.as_tensor(feats).to(dtype).permute(0, 2, 1).unsqueeze(1)
     out = F.relu(_conv_bn(sd, "front.conv1", "front.bn1", x, padding=1))
-    mid = {}
+    mid = {"stem": out}
+    i = 0
     for s, nb in enumerate(blocks):
         for b in range(nb):
             stride = (1 if s == 0 else 2) if b == 0 else 1
             first = s == 0 and b == 0
-            out = _block(sd, "front.layer%d.%d" % (s + 1, b), out, stride, mid if first else None)
+            taps = {}
+            out = _block(sd, "front.layer%d.%d" % (s + 1, b), out, stride, mid if first else None, taps)
+            i += 1
+            mid.update({"b%d.%s" % (i, k): v for k, v in taps.items()})
             if first:
                 mid["block1"] = out
     pooled = asp(sd, out, mid)

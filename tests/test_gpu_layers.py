@@ -407,8 +407,8 @@ def test_tap_api_edges():
     rc, _, _, msg = raw(model, "pooled")
     assert rc == -1 and "no forward" in msg
     # a family without taps
-    rsd = synth.synth_state_dict("ResNet18", 80, 256, seed=42)
-    resnet = NativeSpeakerModel("ResNet18", rsd, feat_dim=80, embed_dim=256, max_batch=2, max_frames=100)
-    resnet(torch.from_numpy(f[:2, :64].copy()))
-    rc, _, _, msg = raw(resnet, "h")
+    csd = synth.synth_state_dict("CAMPPlus", 80, 512, seed=42)
+    cam = NativeSpeakerModel("CAMPPlus", csd, feat_dim=80, embed_dim=512, max_batch=2, max_frames=100)
+    cam(torch.from_numpy(f[:2, :64].copy()))
+    rc, _, _, msg = raw(cam, "h")
     assert rc == -1 and "no activation taps" in msg

@@ -728,6 +728,15 @@ int ws_debug_engine_tap(ws_engine* eng, const char* name, float* dst, int64_t ca
   return eng->model->tap(name, dst, cap_floats, rows, cols, (hipStream_t)stream);
 }
 
+int ws_debug_engine_stop_after(ws_engine* eng, int n_blocks) {
+  if (!eng) { set_error("ws_debug_engine_stop_after: invalid argument"); return WS_ERR_INVALID_ARG; }
+  if (!eng->finalized) {
+    set_error("ws_debug_engine_stop_after: the engine is not finalized (its block list does not exist yet)");
+    return WS_ERR_INVALID_ARG;
+  }
+  return eng->model->set_stop_after(n_blocks);
+}
+
 long long ws_debug_dispatch_report(char* buf, long long cap) {
   if (cap < 0 || (cap > 0 && !buf)) { set_error("ws_debug_dispatch_report: invalid argument"); return WS_ERR_INVALID_ARG; }
   return (long long)dispatch_log_dump(buf, (size_t)cap);

@@ -89,6 +89,22 @@ struct ModelBase : Model {
     bool chain_half = false;     // out1 / cat / y3 / h exist as binary16 only
     bool y2_half = false;        // the last block's Res2 output exists as binary16 only
   } last_chunk;
+  // ---- debug stop point of the 2-D families (ws_debug_engine_stop_after): -1 = the full forward, 0 = return after the
+  // stem, n = after the n-th residual block.  The families with a block loop override set_stop_after to validate n.
+  int stop_after = -1;
+  // what a stopped chunk's tensors are: one block's worth of pointers into the rotating buffers (host side only)
+  struct BlockTaps {
+    int n_exec = -1;             // blocks the last chunk executed (0: the stem alone; -1: nothing to read)
+    bool full = false;           // the chunk ran to its end: the pooling / head tensors exist
+    bool half = false;           // the maps exist as binary16 only (f16 back-end)
+    const float *stem = nullptr, *block = nullptr, *mid = nullptr, *sc = nullptr, *next_y1 = nullptr;
+    int stem_rows = 0, stem_c = 0, rows = 0, block_c = 0, mid_c = 0, next_c = 0, head_rows = 0;
+  } block_taps;
+  // a stopped chunk's embedding rows: zeros, not whatever the caller's buffer held
+  int stop_chunk(float* emb, int B, hipStream_t st) {
+    WS_HIP_CHECK(hipMemsetAsync(emb, 0, (size_t)B * embed_dim * sizeof(float), st));
+    return 0;
+  }
   // one entry of a family's tap table: rows x cols fp32, contiguous at src (null: not produced in fp32)
   int tap_copy(const char* name, const float* src, const char* why_absent, int rows_n, int cols_n, float* dst,
                int64_t cap_floats, int32_t* rows, int32_t* cols, hipStream_t st) {

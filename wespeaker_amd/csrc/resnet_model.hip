@@ -120,6 +120,8 @@ struct ResNetModel : ModelBase {
   int reserve(int max_batch, int max_frames) override {
     int err = 0;
     maxB = max_batch; maxT = max_frames;
+    last_chunk = LastChunk();                  // the taps address the old layout
+    block_taps = BlockTaps();
     // largest activation: stage-1 output (F x T x 32*exp); scratch planes are never larger
     const size_t act = (size_t)maxB * feat_dim * maxT * (size_t)(32 * exp);
     // (the binary16 convolution kernels address a tensor with 32-bit element offsets: one engine chunk keeps
@@ -187,10 +189,15 @@ struct ResNetModel : ModelBase {
     // all convolutions then run on the LDS-DMA kernel (conv form), residuals are read as halfs
     const bool f16io = gemm_precision == 2;
     float* x = buf[0];
+    last_chunk.B = 0;                          // (taps: nothing to read until this chunk has been enqueued)
     WS_LAUNCH(other(4.0 * B * H * (double)W * 33, st, [&] {
       return launch_stem_conv3x3(feats, B, T, feat_dim, arena.at(stem_w), arena.at(stem_b), 32, x, st,
                                  f16io ? reinterpret_cast<uint16_t*>(x) : nullptr, cur_lens[0]);
     }));
+    BlockTaps tp;                              // host-side notes for ws_debug_engine_tap, stored when the chunk ends
+    tp.half = f16io;
+    tp.n_exec = 0; tp.stem = x; tp.stem_rows = B * H * W; tp.stem_c = 32; tp.head_rows = B;
+    if (stop_after == 0) return end_chunk(tp, false, B, T, emb, st);
     // in -> out convolution with the optional residual, in the tensor format of the active back-end
     auto conv = [&](const ConvW& cw, const float* in, int Cin_, float* out, int Cout_, int Hin_, int Win_,
                     int s_, int pad, int act, const float* res, int ldr, int out_lvl) {
@@ -274,6 +281,16 @@ struct ResNetModel : ModelBase {
       x = buf[cur];
       H = Ho; W = Wo;
       lvl = lo;
+      const bool stop = stop_after == (int)bi + 1;
+      if (stop || bi + 1 == blocks.size()) {      // what this block left in the rotation (see the roles above)
+        tp.n_exec = (int)bi + 1; tp.rows = B * Ho * Wo;
+        tp.block = x; tp.block_c = Co;
+        tp.mid = lay.bottleneck ? out : t1; tp.mid_c = P;
+        tp.sc = blk.has_sc ? t2 : nullptr;
+        tp.next_y1 = have_y1 ? buf[y1_idx] : nullptr;
+        tp.next_c = have_y1 ? blocks[bi + 1].planes : 0;
+        if (stop) return end_chunk(tp, false, B, T, emb, st);
+      }
     }
     const int Cl = 256 * exp;           // channels of the last stage
     WS_LAUNCH(other((f16io ? 4.0 : 8.0) * B * H * (double)W * Cl, st, [&] {
@@ -291,7 +308,75 @@ struct ResNetModel : ModelBase {
       WS_LAUNCH(gemm_splitk(a, partial, kSplitK, st));
       WS_LAUNCH(gemm(conv1d(seg2, emb_a, embed_dim, 0, emb, embed_dim, 0, B, 1, 1, ACT_NONE), st));
     }
+    return end_chunk(tp, true, B, T, emb, st);
+  }
+
+  // the chunk is enqueued: remember what it left; a stopped one (ws_debug_engine_stop_after) returns zeros
+  int end_chunk(BlockTaps& tp, bool full, int B, int T, float* emb, hipStream_t st) {
+    tp.full = full;
+    if (!full)
+      if (int r = stop_chunk(emb, B, st)) return r;
+    block_taps = tp;
+    last_chunk.B = B; last_chunk.T = T; last_chunk.prec = gemm_precision;
     return 0;
+  }
+
+  int set_stop_after(int n) override {
+    if (n < -1 || n > (int)blocks.size()) {
+      set_error("ws_debug_engine_stop_after: n_blocks = %d, %s has %d residual blocks (-1 = the full forward, 0 = after "
+                "the stem)", n, name.c_str(), (int)blocks.size());
+      return WS_ERR_INVALID_ARG;
+    }
+    stop_after = n;
+    return WS_OK;
+  }
+
+  // ws_debug_engine_tap: what the last chunk's last executed block left in the four rotating buffers ([b][f][t][c] as
+  // rows = B*H*W, cols = C), and the head's tensors after a full forward
+  int tap(const char* tname, float* dst, int64_t cap_floats, int32_t* rows, int32_t* cols, hipStream_t st) override {
+    if (!last_chunk.B) {
+      set_error("ws_debug_engine_tap: no forward has run on this engine since it was finalized / re-sized");
+      return WS_ERR_INVALID_ARG;
+    }
+    const BlockTaps& t = block_taps;
+    const std::string n = tname;
+    char why[200];
+    const char* half = "the f16 back-end keeps every activation map in binary16 only";
+    auto map = [&](const float* src, int rows_n, int cols_n) {
+      return tap_copy(tname, t.half ? nullptr : src, t.half ? half : why, rows_n, cols_n, dst, cap_floats, rows, cols, st);
+    };
+    if (n == "stem") {
+      std::snprintf(why, sizeof(why), "the last forward ran %d blocks over the stem's buffer: stop it at 0 "
+                    "(ws_debug_engine_stop_after)", t.n_exec);
+      return map(t.n_exec == 0 ? t.stem : nullptr, t.stem_rows, t.stem_c);
+    }
+    if (n == "block" || n == "mid" || n == "sc" || n == "next_y1") {
+      if (t.n_exec < 1) {
+        std::snprintf(why, sizeof(why), "the last forward was stopped after the stem: no block ran");
+        return map(nullptr, 0, 0);
+      }
+      if (n == "block") return map(t.block, t.rows, t.block_c);
+      if (n == "mid") return map(t.mid, t.rows, t.mid_c);
+      if (n == "sc") {
+        std::snprintf(why, sizeof(why), "block %d has no shortcut convolution", t.n_exec);
+        return map(t.sc, t.rows, t.block_c);
+      }
+      std::snprintf(why, sizeof(why), "block %d did not run the fused conv3 + next-conv1 kernel (bneck_c3c1): the next "
+                    "block's conv1 has not run", t.n_exec);
+      return map(t.next_y1, t.rows, t.next_c);
+    }
+    if (n == "pooled" || n == "emb_a") {
+      std::snprintf(why, sizeof(why), "the last forward was stopped after block %d: pooling and the head did not run",
+                    t.n_exec);
+      if (n == "pooled")
+        return tap_copy(tname, t.full ? pooled : nullptr, why, t.head_rows, 2 * stats_dim, dst, cap_floats, rows, cols, st);
+      return tap_copy(tname, !two_emb ? nullptr : (t.full ? emb_a : nullptr),
+                      two_emb ? why : "the model has one embedding layer (no seg_2)", t.head_rows, embed_dim, dst,
+                      cap_floats, rows, cols, st);
+    }
+    set_error("ws_debug_engine_tap: unknown tensor '%s' (%s: stem, block, mid, sc, next_y1, pooled, emb_a)", tname,
+              name.c_str());
+    return WS_ERR_INVALID_ARG;
   }
 
   double flops(int batch, int T) const override {

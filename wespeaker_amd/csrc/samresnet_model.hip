@@ -165,6 +165,7 @@ struct SamResNetModel : ModelBase {
     int err = 0;
     maxB = max_batch; maxT = max_frames;
     last_chunk = LastChunk();
+    block_taps = BlockTaps();
     tap_block1_valid = false;
     // largest activation: every stage-1 map (F x T x in_planes); later stages halve
     const size_t act = (size_t)maxB * feat_dim * maxT * (size_t)m;
@@ -260,6 +261,9 @@ struct SamResNetModel : ModelBase {
     WS_LAUNCH(other(4.0 * B * H * (double)W * (m + 1), st, [&] {
       return launch_stem_conv3x3_any(feats, B, T, feat_dim, arena.at(stem_w), arena.at(stem_b), m, x, st, cur_lens[0]);
     }));
+    BlockTaps tp;                              // host-side notes for ws_debug_engine_tap, stored when the chunk ends
+    tp.n_exec = 0; tp.stem = x; tp.stem_rows = B * H * W; tp.stem_c = m;
+    if (stop_after == 0) return end_chunk(tp, false, B, T, emb, st);
     auto conv = [&](const ConvW& cw, const float* in, int Cin_, float* out, int Cout_, int Hin_, int Win_, int s_,
                     int pad, int act, int out_lvl) {
       ConvGemmParams p = conv2d(cw, in, Cin_, 0, out, Cout_, 0, B, Hin_, Win_, s_, s_, 1, 1, pad, pad, act);
@@ -297,6 +301,14 @@ struct SamResNetModel : ModelBase {
         WS_HIP_CHECK(hipMemcpyAsync(tap_block1, x, (size_t)B * H * W * P * sizeof(float), hipMemcpyDeviceToDevice, st));
         tap_block1_valid = true;
       }
+      const bool stop = stop_after == (int)bi + 1;
+      if (stop || bi + 1 == blocks.size()) {      // what this block left in the rotation
+        tp.n_exec = (int)bi + 1; tp.rows = B * Ho * Wo;
+        tp.block = x; tp.block_c = P;
+        tp.mid = t1; tp.mid_c = P;
+        tp.sc = blk.has_sc ? t2 : nullptr;
+        if (stop) return end_chunk(tp, false, B, T, emb, st);
+      }
     }
     const int Cl = m * 8, D = stats_dim;             // H = F', W = T' here
     {
@@ -311,24 +323,71 @@ struct SamResNetModel : ModelBase {
       return launch_asp_pool(x, logits, B, H, W, Cl, pooled, st, cur_lens[lvl]);
     }));
     WS_LAUNCH(gemm_splitk(conv1d(bott, pooled, 2 * D, 0, emb, embed_dim, 0, B, 1, 1, ACT_NONE), partial, kSplitK, st));
+    tp.head_rows = B * W;                      // rows of hid / logits: the last stage's frames
+    return end_chunk(tp, true, B, T, emb, st);
+  }
+
+  // the chunk is enqueued: remember what it left; a stopped one (ws_debug_engine_stop_after) returns zeros
+  int end_chunk(BlockTaps& tp, bool full, int B, int T, float* emb, hipStream_t st) {
+    tp.full = full;
+    if (!full)
+      if (int r = stop_chunk(emb, B, st)) return r;
+    block_taps = tp;
     last_chunk.B = B; last_chunk.T = T; last_chunk.prec = gemm_precision;
     return 0;
   }
 
+  int set_stop_after(int n) override {
+    if (n < -1 || n > (int)blocks.size()) {
+      set_error("ws_debug_engine_stop_after: n_blocks = %d, %s has %d residual blocks (-1 = the full forward, 0 = after "
+                "the stem)", n, name.c_str(), (int)blocks.size());
+      return WS_ERR_INVALID_ARG;
+    }
+    stop_after = n;
+    return WS_OK;
+  }
+
   // ws_debug_engine_tap: 'block1' = the first block's output [b][f][t][c] as (B*F*T, in_planes) -- a copy made
-  // during the forward, the buffer itself is reused by later blocks --, 'pooled' = the ASP vector (B, 2D)
+  // during the forward, the buffer itself is reused by later blocks.  The last executed block (all of them through
+  // ws_debug_engine_stop_after): 'block' = the gated result, 'mid' = conv1's output, 'sc' = the downsample conv's;
+  // 'stem' when stopped at 0.  After a full forward: 'hid' (B*T', 128), 'logits' (B*T', D), 'pooled' = the ASP vector
   int tap(const char* tname, float* dst, int64_t cap_floats, int32_t* rows, int32_t* cols, hipStream_t st) override {
     if (!last_chunk.B) {
       set_error("ws_debug_engine_tap: no forward has run on this engine since it was finalized / re-sized");
       return WS_ERR_INVALID_ARG;
     }
     const int B = last_chunk.B;
-    if (!std::strcmp(tname, "block1"))
-      return tap_copy(tname, tap_block1_valid ? tap_block1 : nullptr, "the chunk's stage-1 map exceeds the tap buffer",
+    const BlockTaps& t = block_taps;
+    const std::string n = tname;
+    char why[200];
+    if (n == "block1")
+      return tap_copy(tname, tap_block1_valid ? tap_block1 : nullptr,
+                      t.n_exec == 0 ? "the last forward was stopped after the stem: no block ran"
+                                    : "the chunk's stage-1 map exceeds the tap buffer",
                       B * feat_dim * last_chunk.T, m, dst, cap_floats, rows, cols, st);
-    if (!std::strcmp(tname, "pooled"))
-      return tap_copy(tname, pooled, "", B, 2 * stats_dim, dst, cap_floats, rows, cols, st);
-    set_error("ws_debug_engine_tap: unknown tensor '%s' (%s: block1, pooled)", tname, name.c_str());
+    if (n == "stem") {
+      std::snprintf(why, sizeof(why), "the last forward ran %d blocks over the stem's buffer: stop it at 0 "
+                    "(ws_debug_engine_stop_after)", t.n_exec);
+      return tap_copy(tname, t.n_exec == 0 ? t.stem : nullptr, why, t.stem_rows, t.stem_c, dst, cap_floats, rows, cols, st);
+    }
+    if (n == "block" || n == "mid" || n == "sc") {
+      if (t.n_exec < 1)
+        return tap_copy(tname, nullptr, "the last forward was stopped after the stem: no block ran", 0, 0, dst,
+                        cap_floats, rows, cols, st);
+      std::snprintf(why, sizeof(why), "block %d has no downsample convolution", t.n_exec);
+      return tap_copy(tname, n == "block" ? t.block : (n == "mid" ? t.mid : t.sc), why, t.rows, t.block_c, dst,
+                      cap_floats, rows, cols, st);
+    }
+    if (n == "hid" || n == "logits" || n == "pooled") {
+      std::snprintf(why, sizeof(why), "the last forward was stopped after block %d: the ASP head did not run", t.n_exec);
+      if (n == "hid")
+        return tap_copy(tname, t.full ? hid : nullptr, why, t.head_rows, kHidden, dst, cap_floats, rows, cols, st);
+      if (n == "logits")
+        return tap_copy(tname, t.full ? logits : nullptr, why, t.head_rows, stats_dim, dst, cap_floats, rows, cols, st);
+      return tap_copy(tname, t.full ? pooled : nullptr, why, B, 2 * stats_dim, dst, cap_floats, rows, cols, st);
+    }
+    set_error("ws_debug_engine_tap: unknown tensor '%s' (%s: block1, stem, block, mid, sc, hid, logits, pooled)", tname,
+              name.c_str());
     return WS_ERR_INVALID_ARG;
   }
 

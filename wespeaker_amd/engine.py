@@ -8,6 +8,7 @@ reference's callers use (`outputs[-1] if isinstance(outputs, tuple) else outputs
 cli/speaker.py:119-120,165; bin/extract.py:134).  PyTorch is used only to own device memory and
 streams; every FLOP of the forward runs in the HIP library.
 """
+import contextlib
 import ctypes
 from ctypes import c_int64, c_void_p
 
@@ -266,10 +267,32 @@ class NativeSpeakerModel:
                            "ws_engine_check_range")
 
     TAP_NAMES = ("out1", "cat", "h", "y1", "y2", "y3", "se_s", "stats", "bias_img", "pooled")
-    SIMAM_TAP_NAMES = ("block1", "pooled")    # SimAM_ResNet*_ASP: first block's output (B*F*T, in_planes), ASP vector
+    # SimAM_ResNet*_ASP: block1 = a copy of the first block's output (B*F*T, in_planes); stem / block / mid / sc = the
+    # last executed block's tensors (stop_after); hid / logits / pooled = the ASP head's, after a full forward
+    SIMAM_TAP_NAMES = ("block1", "stem", "block", "mid", "sc", "hid", "logits", "pooled")
+    # ResNet*: the last executed block's tensors, rows = B*H*W in [b][f][t] order (stop_after picks the block); stem only
+    # when stopped at 0, next_y1 only where the fused conv3 + conv1 kernel ran, pooled / emb_a after a full forward
+    RESNET_TAP_NAMES = ("stem", "block", "mid", "sc", "next_y1", "pooled", "emb_a")
+
+    def stop_after(self, n_blocks):
+        """Diagnostic (ResNet / SimAM-ResNet; ws_debug_engine_stop_after): every later forward returns after the stem
+        (0) or after the n-th residual block, its embeddings all zero, so that tap() reads that block's tensors.
+        -1 restores the full forward.  Prefer `with model.stopped_after(n): ...`, which always restores it."""
+        _lib.check(_lib.lib().ws_debug_engine_stop_after(self._h, int(n_blocks)), "ws_debug_engine_stop_after")
+        return self
+
+    @contextlib.contextmanager
+    def stopped_after(self, n_blocks):
+        """`with model.stopped_after(n): model(feats)` -- stop_after(n) for the body, the full forward again after it."""
+        self.stop_after(n_blocks)
+        try:
+            yield self
+        finally:
+            self.stop_after(-1)
 
     def tap_shape(self, name):
-        """(rows, cols) of a tap without copying it (ws_debug_engine_tap with a NULL destination)."""
+        """(rows, cols) of a tap without copying it (ws_debug_engine_tap with a NULL destination).  Names: TAP_NAMES
+        (ECAPA-TDNN), RESNET_TAP_NAMES, SIMAM_TAP_NAMES."""
         rows, cols = ctypes.c_int32(0), ctypes.c_int32(0)
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().ws_debug_engine_tap(self._h, name.encode(), None, 0, ctypes.byref(rows),
@@ -281,6 +304,9 @@ class NativeSpeakerModel:
         """Diagnostic: a copy of the fp32 activation `name` (TAP_NAMES; ECAPA-TDNN) that the last chunk of the last
         forward left in the engine's workspace, as a (rows, cols) tensor on the GPU -- rows = B * T_slot for the
         frame-level tensors, B for se_s / stats / bias_img / pooled; channels contiguous (ws_debug_engine_tap).
+        ResNet (RESNET_TAP_NAMES) and SimAM-ResNet (SIMAM_TAP_NAMES): stem / block / mid / sc / next_y1 of the last
+        EXECUTED block as (B * H * W, C) in [b][f][t][c] order -- the models rotate four buffers, so an earlier block is
+        read with stopped_after(n) --, and pooled / emb_a (ResNet), hid / logits / pooled (SimAM) after a full forward.
         Raises NativeError for a tensor that forward did not leave in fp32."""
         rows, cols = self.tap_shape(name)
         out = torch.empty((rows, cols), dtype=torch.float32, device=self.device)
