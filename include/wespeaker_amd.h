@@ -62,9 +62,10 @@ typedef void* ws_stream;                /* hipStream_t */
 /* Bumped whenever an exported signature changes (101: ws_plda_stats takes `emb_is_f64` and a void* table since
  * round 2 -- a caller built against 100 would pass shifted arguments; 104: ws_frontend_set_cmvn / ws_cmvn added, the
  * `cmn` flags now mean "apply the frontend's CMVN"; 105: ws_forward_ragged_cmvn added; 106: ws_debug_engine_tap added;
- * 107: ws_debug_engine_stop_after added).
+ * 107: ws_debug_engine_stop_after added; 108: ws_debug_engine_stop_after and ws_debug_engine_tap serve CAM++ -- a
+ * caller that relied on their refusing that family sees other results).
  * ws_version() returns the library's value: compare it with the header's before calling anything else. */
-#define WS_VERSION 107
+#define WS_VERSION 108
 WS_API int ws_version(void);
 WS_API const char* ws_last_error(void);
 /* Number of fbank frames for num_samples at snip_edges=True (25 ms / 10 ms):
@@ -296,23 +297,42 @@ WS_API int ws_debug_fbank_mode(int mode);
  * SimAM-ResNet names: block (the gated result), mid (conv1's output), sc (the downsample convolution's output), and
  * after a full forward hid (B * T', 128: the first attention layer), logits (B * T', D; D in f * C + c order),
  * pooled (B, 2D); block1 = a copy of the first block's output made during the forward.
+ * CAM++ names (tests/test_gpu_campplus_layers.py).  The FCM head rotates three buffers and the trunk ping-pongs two, so
+ * a stop point (ws_debug_engine_stop_after, stages 0 .. 9) selects what is read:
+ *   stem     the stem's output, [b][f][t][32] as rows = B * F * T      -- only when stopped at 0
+ *   block    the last executed FCM residual block's output [b][f][t][32] (F = 40 after blocks 1 - 2, 20 after 3 - 4)
+ *   mid      its conv1 output                                -- stops 1 .. 4 (head.conv2 writes over it)
+ *   sc       its shortcut convolution's output               -- blocks 1 and 3
+ *   fcm      head.conv2's output [b][F / 8][t][32]           -- from stop 5 on
+ *   tdnn     the TDNN layer's output (B * T', 128), T' = (T - 1) / 2 + 1      -- stops 6 and 7
+ *   dense    the last executed dense block's whole buffer (B * T', 512 / 1024 / 1024): the block input (the TDNN or
+ *            the previous transit output) followed by 32 columns per layer       -- from stop 7 on
+ *   transit  that block's transit output (B * T', 256 / 512 / 512), gathered from the next buffer's row stride
+ *   h        (B * T', 128) the LAST layer's bottleneck output (after BN-ReLU) of that block, and
+ *   mask     (B * segments, 32) that layer's context mask, segments = ceil(T' / 100) per slot -- only where the
+ *            three-launch path ran (f16x3 at every length, fp32 above T' = 128): cam_dense_block_kernel keeps both in
+ *            LDS; WS_PREC_F16 with one segment and T' >= 64 keeps h in binary16 only (mask still taps)
+ *   pooled   (B, 1024)                                       -- only after a full forward
  * Rows beyond an utterance's own frames (ragged forward) are the zeros the kernels stored there.
  * dst DEVICE float32[cap_floats], or NULL to ask for the shape only; rows / cols (HOST, may be NULL) receive it.
  * WS_ERR_INVALID_ARG (message in ws_last_error): unknown name; a tensor the last forward did not leave in fp32
  * (WS_PREC_F16 with T >= 64 keeps the block chain and h in binary16 only, and every ResNet map; stats / bias_img exist
  * for GLOB models; a block without a shortcut has no sc, an unfused one no next_y1, a stopped forward no pooled);
- * a model family without taps (CAM++); no forward since the engine was finalized / its workspace re-sized.
+ * a CAM++ tensor the stop point does not leave (above); no forward since the engine was finalized / its workspace
+ * re-sized.
  * WS_ERR_CAPACITY: cap_floats < rows * cols.  The forward path itself is unchanged: a few host-side integers remember
  * the last chunk. */
 WS_API int ws_debug_engine_tap(ws_engine* eng, const char* name, float* dst, int64_t cap_floats, int32_t* rows,
                                int32_t* cols, ws_stream stream);
-/* Debug stop point of the 2-D families (ResNet, SimAM-ResNet; no reference counterpart): every later forward on this
+/* Debug stop point of the 2-D families and CAM++ (ResNet, SimAM-ResNet, CAMPPlus; no reference counterpart): every later forward on this
  * engine returns after the stem (n_blocks = 0) or after the last launch of the n-th residual block (a fused
  * conv3 + next-conv1 launch belongs to block n), so that ws_debug_engine_tap can read what those launches left.
  * Pooling and the head do not run; the embedding output is zero-filled on the stream.  -1 (the default) = the full
  * forward: with it no launch, store or dispatch decision differs from a library without the stop point (one host-side
- * integer, tested once per block).  WS_ERR_INVALID_ARG: n_blocks < -1 or beyond the model's block count; a family
- * without a block loop (ECAPA-TDNN, CAM++); an engine that is not finalized. */
+ * integer, tested once per block).  CAM++ counts stages instead of residual blocks: 0 = the stem, 1 .. 4 = the FCM
+ * residual blocks, 5 = head.conv2, 6 = the TDNN layer, 7 / 8 / 9 = dense block 1 / 2 / 3 AND its transit.
+ * WS_ERR_INVALID_ARG: n_blocks < -1 or beyond the model's block / stage count; a family without a block loop
+ * (ECAPA-TDNN); an engine that is not finalized. */
 WS_API int ws_debug_engine_stop_after(ws_engine* eng, int n_blocks);
 /* Algorithmic FLOPs (2 x MACs of every conv/linear) of one forward at (batch, num_frames). */
 WS_API double ws_engine_flops(const ws_engine* eng, int batch, int num_frames);

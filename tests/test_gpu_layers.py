@@ -406,9 +406,13 @@ def test_tap_api_edges():
     model.reserve(4, 100)
     rc, _, _, msg = raw(model, "pooled")
     assert rc == -1 and "no forward" in msg
-    # a family without taps
+    # another family's names: CAM++ has its own table (tests/test_gpu_campplus_layers.py) and refuses, with the reason,
+    # the tensors that its fused dense-block kernel keeps in LDS
     csd = synth.synth_state_dict("CAMPPlus", 80, 512, seed=42)
     cam = NativeSpeakerModel("CAMPPlus", csd, feat_dim=80, embed_dim=512, max_batch=2, max_frames=100)
     cam(torch.from_numpy(f[:2, :64].copy()))
+    rc, _, _, msg = raw(cam, "out1")
+    assert rc == -1 and "unknown tensor 'out1'" in msg and "CAMPPlus" in msg
     rc, _, _, msg = raw(cam, "h")
-    assert rc == -1 and "no activation taps" in msg
+    assert rc == -1 and "stay in LDS" in msg
+    assert raw(cam, "dense")[:3] == (0, 2 * 32, 1024)

@@ -44,6 +44,21 @@ struct CamppModel : ModelBase {
   float *fa = nullptr, *fb = nullptr, *fc = nullptr, *xbuf = nullptr, *xbuf2 = nullptr, *hbuf = nullptr,
         *mask = nullptr, *pooled = nullptr, *partial = nullptr, *colsum = nullptr;
   int max_segs = 1;
+  // ---- debug stop points and taps (ws_debug_engine_stop_after / ws_debug_engine_tap).  Stage numbering: 0 = the stem,
+  // 1..4 = the FCM residual blocks, 5 = head.conv2, 6 = the TDNN layer, 7 / 8 / 9 = dense block 1 / 2 / 3 with its
+  // transit.  Host-side notes on what the last chunk left in fa / fb / fc, xbuf / xbuf2, hbuf and mask.
+  static constexpr int kStages = 10;
+  struct CamTaps {
+    int stage = -1;              // last executed stage (kStages - 1 on a full forward; -1: nothing to read)
+    bool full = false;           // the chunk ran to its end: pooled exists
+    bool half = false;           // the FCM maps exist as binary16 only (f16 back-end)
+    int B = 0, T = 0, Tp = 0, segs = 0;
+    const float *stem = nullptr, *block = nullptr, *mid = nullptr, *sc = nullptr, *fcm = nullptr, *tdnn = nullptr,
+                *dense = nullptr, *transit = nullptr, *h = nullptr, *mask = nullptr;
+    int n_res = 0, res_H = 0, fcm_H = 0, tdnn_ld = 0, dense_ld = 0, transit_ld = 0, transit_c = 0;
+    const char* why_no_h = "";   // h / mask absent: the reason
+    const char* why_no_mask = "";
+  } cam_taps;
 
   CamppModel(int fd, int ed) : ModelBase("CAMPPlus", fd, ed) {}
 
@@ -139,6 +154,8 @@ struct CamppModel : ModelBase {
   int reserve(int max_batch, int max_frames) override {
     int err = 0;
     maxB = max_batch; maxT = max_frames;
+    last_chunk = LastChunk();                  // the taps address the old layout
+    cam_taps = CamTaps();
     const size_t img = (size_t)maxB * feat_dim * maxT * 32;        // FCM full-resolution activation
     // (32-bit element offsets in the binary16 convolution kernels: one engine chunk stays below 2^31 elements)
     if (img >= (size_t)1 << 31) {
@@ -178,10 +195,15 @@ struct CamppModel : ModelBase {
     // layer that consumes them) run on the LDS-DMA kernel in convolution form
     const bool f16io = gemm_precision == 2;
     int H = feat_dim;
+    last_chunk.B = 0;                          // (taps: nothing to read until this chunk has been enqueued)
     WS_LAUNCH(other(4.0 * B * H * (double)T * 33, st, [&] {
       return launch_stem_conv3x3(feats, B, T, feat_dim, arena.at(stem_w), arena.at(stem_b), 32, fa, st,
                                  f16io ? reinterpret_cast<uint16_t*>(fa) : nullptr, L0);
     }));
+    CamTaps tp;                                // host-side notes for ws_debug_engine_tap, stored when the chunk ends
+    tp.half = f16io; tp.B = B; tp.T = T; tp.Tp = (T - 1) / 2 + 1;
+    tp.stem = fa;
+    if (stop_after == 0) return end_chunk(tp, 0, false, emb, st);
     auto to16 = [&](ConvGemmParams& p, const float* in, float* out, const float* res) {
       if (!f16io) { if (res) { p.residual = res; p.ldr = 32; p.r_off = 0; } return; }
       p.A16 = reinterpret_cast<const uint16_t*>(in); p.lda16 = 32;
@@ -212,8 +234,12 @@ struct CamppModel : ModelBase {
       to16(p2, t1, out, r);
       p2.row_len = L0;
       WS_LAUNCH(gemm(p2, st));
+      // what this block left in fa / fb / fc: its result, conv1's output, the shortcut convolution's output
+      tp.stem = nullptr; tp.block = out; tp.mid = t1; tp.sc = res[i].has_sc ? t2 : nullptr;
+      tp.n_res = i + 1; tp.res_H = Ho;
       if (!res[i].has_sc) { float* tmp = x; x = t2; t2 = tmp; }
       H = Ho;
+      if (stop_after == i + 1) return end_chunk(tp, i + 1, false, emb, st);
     }
     {   // head.conv2: 3x3 stride (2,1) + BN + ReLU  -> [b][F'][T][32]
       ConvGemmParams ph = conv2d(head_conv2, x, 32, 0, t1, 32, 0, B, H, T, 2, 1, 1, 1, 1, 1, ACT_RELU);
@@ -221,6 +247,9 @@ struct CamppModel : ModelBase {
       ph.row_len = L0;
       WS_LAUNCH(gemm(ph, st));
       H = (H - 1) / 2 + 1;
+      tp.mid = nullptr;                        // (head.conv2 wrote over block 4's conv1 output)
+      tp.fcm = t1; tp.fcm_H = H;
+      if (stop_after == 5) return end_chunk(tp, 5, false, emb, st);
     }
     // ---------------- TDNN (k5, stride 2) over the (F' x T) image -> [B*T'][128] at channel 0 of xbuf
     const int Tp = (T - 1) / 2 + 1;
@@ -232,6 +261,8 @@ struct CamppModel : ModelBase {
       to16(pt0, t1, nullptr, nullptr);          // binary16 input, fp32 output (the dense blocks stay fp32)
       pt0.row_len = L1;
       WS_LAUNCH(gemm(pt0, st));
+      tp.tdnn = X; tp.tdnn_ld = ldx;
+      if (stop_after == 6) return end_chunk(tp, 6, false, emb, st);
     }
     const int segs = (Tp + 99) / 100;
     int ch = 128;
@@ -240,6 +271,7 @@ struct CamppModel : ModelBase {
       // (cam_dense_block_kernel); a block the launch cannot take (more layers than its argument block holds, an
       // unaligned trunk buffer) falls back to one launch per layer below
       bool block_done = false;
+      bool h_is_half = false;
       if (gemm_precision == 0 && (int)layers[k].size() <= WS_CAM_MAX_LAYERS &&
           !layers[k].empty() && (reinterpret_cast<uintptr_t>(X) & 127) == 0 && (ldx & 31) == 0) {
         bool ok = true;
@@ -300,6 +332,7 @@ struct CamppModel : ModelBase {
         // as binary16 (hbuf reused), read by the conv DMA kernel
         const bool h_half = f16io && ctx_from_colsum;
         if (h_half) { p1.D = nullptr; p1.D16 = reinterpret_cast<uint16_t*>(hbuf); p1.ldd16 = 128; }
+        h_is_half = h_half;
         p1.row_len = L1;
         WS_LAUNCH(gemm(p1, st));
         // context mask m[b][seg][32]
@@ -324,9 +357,19 @@ struct CamppModel : ModelBase {
       pt.pre_scale = arena.at(transit[k].pre_s); pt.pre_shift = arena.at(transit[k].pre_b);
       pt.row_len = L1;
       WS_LAUNCH(gemm(pt, st));
+      // what this block left: its whole buffer, the transit output at the next buffer's row stride, and -- where the
+      // three-launch path ran -- the last layer's bottleneck output and mask
+      tp.dense = X; tp.dense_ld = ldx; tp.transit = Xn; tp.transit_ld = ld_next; tp.transit_c = ch / 2; tp.segs = segs;
+      if (k > 0) tp.tdnn = nullptr;            // (transit 2 wrote over block 1's buffer)
+      const bool generic = !block_done && !(gemm_precision == 0 && cam_dense_fused_applies(Tp, layers[k][0].cin, kDil[k]));
+      tp.h = generic && !h_is_half ? hbuf : nullptr;
+      tp.mask = generic ? mask : nullptr;
+      tp.why_no_mask = "cam_dense_block_kernel ran the block: the bottleneck and the mask stay in LDS";
+      tp.why_no_h = generic ? "the f16 back-end keeps the bottleneck output in binary16 only" : tp.why_no_mask;
       float* tmp = X; X = Xn; Xn = tmp;
       ldx = ld_next;
       ch /= 2;
+      if (stop_after == 7 + k) return end_chunk(tp, 7 + k, false, emb, st);
     }
     // out_nonlinear BN-ReLU fused into TSTP, then dense 1x1 + BN(affine=False)
     WS_LAUNCH(other(8.0 * B * (double)Tp * ch, st, [&] {
@@ -334,7 +377,91 @@ struct CamppModel : ModelBase {
     }));
     WS_LAUNCH(gemm_splitk(conv1d(dense, pooled, 2 * ch, 0, emb, embed_dim, 0, B, 1, 1, ACT_NONE),
                           partial, kSplitK, st));
+    return end_chunk(tp, kStages - 1, true, emb, st);
+  }
+
+  // the chunk is enqueued: remember what it left; a stopped one (ws_debug_engine_stop_after) returns zeros
+  int end_chunk(CamTaps& tp, int stage, bool full, float* emb, hipStream_t st) {
+    tp.stage = stage; tp.full = full;
+    if (!full)
+      if (int r = stop_chunk(emb, tp.B, st)) return r;
+    cam_taps = tp;
+    last_chunk.B = tp.B; last_chunk.T = tp.T; last_chunk.prec = gemm_precision;
     return 0;
+  }
+
+  int set_stop_after(int n) override {
+    if (n < -1 || n >= kStages) {
+      set_error("ws_debug_engine_stop_after: n = %d, %s has %d stop points 0 .. %d (0 the stem, 1-4 the FCM residual "
+                "blocks, 5 head.conv2, 6 the TDNN layer, 7-9 dense block 1-3 with its transit; -1 = the full forward)",
+                n, name.c_str(), kStages, kStages - 1);
+      return WS_ERR_INVALID_ARG;
+    }
+    stop_after = n;
+    return WS_OK;
+  }
+
+  // ws_debug_engine_tap: what the last chunk's last executed stages left in the workspace (see CamTaps)
+  int tap(const char* tname, float* dst, int64_t cap_floats, int32_t* rows, int32_t* cols, hipStream_t st) override {
+    if (!last_chunk.B) {
+      set_error("ws_debug_engine_tap: no forward has run on this engine since it was finalized / re-sized");
+      return WS_ERR_INVALID_ARG;
+    }
+    const CamTaps& t = cam_taps;
+    const std::string n = tname;
+    char why[200] = "";
+    const char* half = "the f16 back-end keeps the FCM maps in binary16 only";
+    auto map = [&](const float* src, int H) {       // an FCM map [b][f][t][32]
+      return tap_copy(tname, t.half ? nullptr : src, t.half ? half : why, t.B * H * t.T, 32, dst, cap_floats, rows, cols, st);
+    };
+    const int M = t.B * t.Tp;
+    if (n == "stem") {
+      std::snprintf(why, sizeof(why), "the last forward ran on to stage %d and FCM block 1 wrote over the stem: stop it "
+                    "at 0 (ws_debug_engine_stop_after)", t.stage);
+      return map(t.stem, feat_dim);
+    }
+    if (n == "block" || n == "mid" || n == "sc") {
+      if (t.n_res < 1) {
+        std::snprintf(why, sizeof(why), "the last forward was stopped after the stem: no FCM block ran");
+        return map(nullptr, 0);
+      }
+      if (n == "block") return map(t.block, t.res_H);
+      if (n == "mid") {
+        std::snprintf(why, sizeof(why), "head.conv2 wrote over FCM block 4's conv1 output: stop at 1 .. 4");
+        return map(t.mid, t.res_H);
+      }
+      std::snprintf(why, sizeof(why), "FCM block %d has no shortcut convolution", t.n_res);
+      return map(t.sc, t.res_H);
+    }
+    if (n == "fcm") {
+      std::snprintf(why, sizeof(why), "the last forward was stopped at %d, before head.conv2 (stop 5)", t.stage);
+      return map(t.fcm, t.fcm_H);
+    }
+    if (n == "tdnn") {
+      if (t.stage < 6)
+        std::snprintf(why, sizeof(why), "the last forward was stopped at %d, before the TDNN layer (stop 6)", t.stage);
+      else
+        std::snprintf(why, sizeof(why), "the last forward ran on to stage %d and transit 2 wrote over dense block 1's "
+                      "buffer: stop at 6 or 7", t.stage);
+      return tap_copy(tname, t.tdnn, why, M, 128, dst, cap_floats, rows, cols, st, t.tdnn_ld);
+    }
+    if (n == "dense" || n == "transit" || n == "h" || n == "mask") {
+      if (!t.dense) {
+        std::snprintf(why, sizeof(why), "the last forward was stopped at %d: no dense block ran (stops 7 .. 9)", t.stage);
+        return tap_copy(tname, nullptr, why, 0, 0, dst, cap_floats, rows, cols, st);
+      }
+      if (n == "dense") return tap_copy(tname, t.dense, why, M, t.dense_ld, dst, cap_floats, rows, cols, st);
+      if (n == "transit") return tap_copy(tname, t.transit, why, M, t.transit_c, dst, cap_floats, rows, cols, st, t.transit_ld);
+      if (n == "h") return tap_copy(tname, t.h, t.why_no_h, M, 128, dst, cap_floats, rows, cols, st);
+      return tap_copy(tname, t.mask, t.why_no_mask, t.B * t.segs, 32, dst, cap_floats, rows, cols, st);
+    }
+    if (n == "pooled") {
+      std::snprintf(why, sizeof(why), "the last forward was stopped at %d: pooling and the head did not run", t.stage);
+      return tap_copy(tname, t.full ? pooled : nullptr, why, t.B, 1024, dst, cap_floats, rows, cols, st);
+    }
+    set_error("ws_debug_engine_tap: unknown tensor '%s' (%s: stem, block, mid, sc, fcm, tdnn, dense, transit, h, mask, "
+              "pooled)", tname, name.c_str());
+    return WS_ERR_INVALID_ARG;
   }
 
   double flops(int batch, int T) const override {

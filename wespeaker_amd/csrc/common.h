@@ -208,16 +208,16 @@ struct Model {
   // only).  Families without taps keep this default.
   virtual int tap(const char* name, float* dst, int64_t cap_floats, int32_t* rows, int32_t* cols, hipStream_t stream) {
     (void)dst; (void)cap_floats; (void)rows; (void)cols; (void)stream;
-    set_error("ws_debug_engine_tap: this model family has no activation taps (tensor '%s'; ECAPA-TDNN, ResNet and "
-              "SimAM-ResNet have them)", name);
+    set_error("ws_debug_engine_tap: this model family has no activation taps (tensor '%s'; ECAPA-TDNN, ResNet, "
+              "SimAM-ResNet and CAM++ have them)", name);
     return WS_ERR_INVALID_ARG;
   }
   // ws_debug_engine_stop_after: the 2-D families (ResNet, SimAM-ResNet) return from forward_chunk after the stem
-  // (0) or after the n-th residual block, with the embedding zero-filled; -1 = the full forward.  Families without a
-  // block loop keep this default.
+  // (0) or after the n-th residual block, CAM++ after stage n (campplus_model.hip), with the embedding zero-filled;
+  // -1 = the full forward.  Families without a block loop keep this default.
   virtual int set_stop_after(int n_blocks) {
     set_error("ws_debug_engine_stop_after: this model family has no residual-block loop to stop in (n_blocks = %d; "
-              "ResNet and SimAM-ResNet have one)", n_blocks);
+              "ResNet and SimAM-ResNet have one, CAM++ has stages)", n_blocks);
     return WS_ERR_INVALID_ARG;
   }
   virtual int set_precision(int mode) = 0;   // 0 exact fp32 MFMA, 1 split-f16 x3 MFMA

@@ -89,8 +89,9 @@ struct ModelBase : Model {
     bool chain_half = false;     // out1 / cat / y3 / h exist as binary16 only
     bool y2_half = false;        // the last block's Res2 output exists as binary16 only
   } last_chunk;
-  // ---- debug stop point of the 2-D families (ws_debug_engine_stop_after): -1 = the full forward, 0 = return after the
-  // stem, n = after the n-th residual block.  The families with a block loop override set_stop_after to validate n.
+  // ---- debug stop point of the 2-D families and CAM++ (ws_debug_engine_stop_after): -1 = the full forward, 0 = return
+  // after the stem, n = after the n-th residual block (CAM++: after stage n).  The families with a block loop override
+  // set_stop_after to validate n.
   int stop_after = -1;
   // what a stopped chunk's tensors are: one block's worth of pointers into the rotating buffers (host side only)
   struct BlockTaps {
@@ -105,9 +106,10 @@ struct ModelBase : Model {
     WS_HIP_CHECK(hipMemsetAsync(emb, 0, (size_t)B * embed_dim * sizeof(float), st));
     return 0;
   }
-  // one entry of a family's tap table: rows x cols fp32, contiguous at src (null: not produced in fp32)
+  // one entry of a family's tap table: rows x cols fp32 at src (null: not produced in fp32), contiguous or -- src_ld > 0
+  // -- with a row stride of src_ld floats (CAM++'s transit output lies in the next dense block's wider buffer)
   int tap_copy(const char* name, const float* src, const char* why_absent, int rows_n, int cols_n, float* dst,
-               int64_t cap_floats, int32_t* rows, int32_t* cols, hipStream_t st) {
+               int64_t cap_floats, int32_t* rows, int32_t* cols, hipStream_t st, int src_ld = 0) {
     if (!src) {
       set_error("ws_debug_engine_tap: the last forward left no fp32 '%s' (%s)", name, why_absent);
       return WS_ERR_INVALID_ARG;
@@ -121,7 +123,12 @@ struct ModelBase : Model {
                 (long long)cap_floats);
       return WS_ERR_CAPACITY;
     }
-    WS_HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (src_ld > 0 && src_ld != cols_n) {
+      WS_HIP_CHECK(hipMemcpy2DAsync(dst, (size_t)cols_n * sizeof(float), src, (size_t)src_ld * sizeof(float),
+                                    (size_t)cols_n * sizeof(float), (size_t)rows_n, hipMemcpyDeviceToDevice, st));
+    } else {
+      WS_HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
     return WS_OK;
   }
 

@@ -273,10 +273,15 @@ class NativeSpeakerModel:
     # ResNet*: the last executed block's tensors, rows = B*H*W in [b][f][t] order (stop_after picks the block); stem only
     # when stopped at 0, next_y1 only where the fused conv3 + conv1 kernel ran, pooled / emb_a after a full forward
     RESNET_TAP_NAMES = ("stem", "block", "mid", "sc", "next_y1", "pooled", "emb_a")
+    # CAMPPlus: stop_after counts stages (0 stem, 1-4 FCM residual blocks, 5 head.conv2, 6 TDNN, 7-9 dense block 1-3 with
+    # its transit); stem / block / mid / sc / fcm = FCM maps (B*F*T, 32), tdnn / dense / transit / h = (B*T', cols),
+    # mask = (B*segments, 32); h and mask only where the three-launch dense path ran; pooled after a full forward
+    CAMPPLUS_TAP_NAMES = ("stem", "block", "mid", "sc", "fcm", "tdnn", "dense", "transit", "h", "mask", "pooled")
 
     def stop_after(self, n_blocks):
-        """Diagnostic (ResNet / SimAM-ResNet; ws_debug_engine_stop_after): every later forward returns after the stem
-        (0) or after the n-th residual block, its embeddings all zero, so that tap() reads that block's tensors.
+        """Diagnostic (ResNet / SimAM-ResNet / CAMPPlus; ws_debug_engine_stop_after): every later forward returns after
+        the stem (0) or after the n-th residual block (CAMPPlus: after stage n, see CAMPPLUS_TAP_NAMES), its embeddings
+        all zero, so that tap() reads that block's tensors.
         -1 restores the full forward.  Prefer `with model.stopped_after(n): ...`, which always restores it."""
         _lib.check(_lib.lib().ws_debug_engine_stop_after(self._h, int(n_blocks)), "ws_debug_engine_stop_after")
         return self
@@ -292,7 +297,7 @@ class NativeSpeakerModel:
 
     def tap_shape(self, name):
         """(rows, cols) of a tap without copying it (ws_debug_engine_tap with a NULL destination).  Names: TAP_NAMES
-        (ECAPA-TDNN), RESNET_TAP_NAMES, SIMAM_TAP_NAMES."""
+        (ECAPA-TDNN), RESNET_TAP_NAMES, SIMAM_TAP_NAMES, CAMPPLUS_TAP_NAMES."""
         rows, cols = ctypes.c_int32(0), ctypes.c_int32(0)
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().ws_debug_engine_tap(self._h, name.encode(), None, 0, ctypes.byref(rows),
