@@ -8,7 +8,7 @@ are too large to commit, e.g. 6 M-parameter weight sets).
 
 State-dict key names/shapes are the reference's parameter names
 (wespeaker/models/ecapa_tdnn.py:160-206, pooling_layers.py:97-117,
-resnet.py:110-169, campplus.py:333-407) because the weight ingestion path
+resnet.py:110-169, campplus.py:333-407, eres2net.py:243-335) because the weight ingestion path
 (`load_model` -> `avg_model.pt`) is keyed by them.
 """
 from collections import OrderedDict
@@ -206,6 +206,63 @@ def synth_simam_resnet_state_dict(model_name="SimAM_ResNet34_ASP", feat_dim=80, 
     return g.sd
 
 
+ERES2NET_LAYOUTS = {      # reference eres2net.py:394-430: (m_channels, baseWidth, scale, expansion); blocks [3, 4, 6, 3]
+    "ERes2Net34_Base": (32, 32, 2, 2), "ERes2Net34_Large": (64, 32, 2, 2), "ERes2Net34_aug": (64, 24, 3, 4),
+}
+
+
+def synth_eres2net_state_dict(name="ERes2Net34_Base", feat_dim=80, embed_dim=512, two_emb_layer=False, seed=42):
+    """ERes2Net34_Base / _Large / _aug (eres2net.py:243-335), keys in the module's own order.  The gains keep the maps
+    O(1) through the 16 blocks: the branch chain and conv3 are damped so that the residual sum neither dies out nor
+    climbs to the Hardtanh(0, 20) ceiling, and the AFF logits are wide enough for the tanh gate to move."""
+    m, base_width, scale, exp = ERES2NET_LAYOUTS[name]
+    g = _Init(seed)
+
+    def aff(p, c):
+        g.conv(p + ".local_att.0", c // 4, 2 * c, 1, 1, gain=1.0)
+        g.bn(p + ".local_att.1", c // 4)
+        g.conv(p + ".local_att.3", c, c // 4, 1, 1, gain=2.0)
+        g.bn(p + ".local_att.4", c)
+
+    g.conv("conv1", m, 1, 3, 3, bias=False)
+    g.bn("bn1", m)
+    cin = m
+    for s, nb in enumerate((3, 4, 6, 3)):
+        planes = m * (2 ** s)
+        width = int(np.floor(planes * (base_width / 64.0)))
+        for b in range(nb):
+            stride = (1 if s == 0 else 2) if b == 0 else 1
+            p = "layer%d.%d" % (s + 1, b)
+            g.conv(p + ".conv1", width * scale, cin, 1, 1, bias=False)
+            g.bn(p + ".bn1", width * scale)
+            if s >= 2:
+                g.conv(p + ".conv2_1", width, width, 3, 3, bias=False, gain=1.0)
+                g.bn(p + ".bn2_1", width)
+            for i in range(scale if s < 2 else scale - 1):
+                g.conv(p + ".convs.%d" % i, width, width, 3, 3, bias=False, gain=1.0)
+            for i in range(scale if s < 2 else scale - 1):
+                g.bn(p + ".bns.%d" % i, width)
+            if s >= 2:
+                for i in range(scale - 1):
+                    aff(p + ".fuse_models.%d" % i, width)
+            g.conv(p + ".conv3", planes * exp, width * scale, 1, 1, bias=False, gain=0.25)
+            g.bn(p + ".bn3", planes * exp)
+            if stride != 1 or cin != planes * exp:
+                g.conv(p + ".shortcut.0", planes * exp, cin, 1, 1, bias=False, gain=1.0)
+                g.bn(p + ".shortcut.1", planes * exp)
+            cin = planes * exp
+    for k in range(3):
+        c = m * exp * (2 ** k)
+        g.conv("layer%d_downsample" % (k + 1), 2 * c, c, 3, 3, bias=False, gain=1.0)
+    for k, fn in enumerate(("fuse_mode12", "fuse_mode123", "fuse_mode1234")):
+        aff(fn, m * exp * (2 ** (k + 1)))
+    g.linear("seg_1", embed_dim, (feat_dim // 8) * m * 8 * exp * 2)
+    if two_emb_layer:
+        g.bn("seg_bn_1", embed_dim, affine=False)
+        g.linear("seg_2", embed_dim, embed_dim)
+    return g.sd
+
+
 def synth_campplus_state_dict(feat_dim=80, embed_dim=512, seed=42):
     g = _Init(seed)
     g.conv("head.conv1", 32, 1, 3, 3, bias=False)
@@ -261,6 +318,9 @@ def synth_state_dict(model_name, feat_dim=80, embed_dim=None, seed=42, **kw):
     if model_name.startswith("CAMPPlus"):
         kw.pop("pooling_func", None)
         return synth_campplus_state_dict(feat_dim, embed_dim or 512, seed=seed)
+    if model_name.startswith("ERes2Net"):
+        kw.pop("pooling_func", None)
+        return synth_eres2net_state_dict(model_name, feat_dim, embed_dim or 512, seed=seed, **kw)
     raise KeyError("no synthetic weights for model %r" % model_name)
 
 

@@ -63,9 +63,10 @@ typedef void* ws_stream;                /* hipStream_t */
  * round 2 -- a caller built against 100 would pass shifted arguments; 104: ws_frontend_set_cmvn / ws_cmvn added, the
  * `cmn` flags now mean "apply the frontend's CMVN"; 105: ws_forward_ragged_cmvn added; 106: ws_debug_engine_tap added;
  * 107: ws_debug_engine_stop_after added; 108: ws_debug_engine_stop_after and ws_debug_engine_tap serve CAM++ -- a
- * caller that relied on their refusing that family sees other results).
+ * caller that relied on their refusing that family sees other results; 109: ws_debug_aff_fuse added, ws_engine_create
+ * knows the ERes2Net34 names, ws_debug_engine_tap / ws_debug_engine_stop_after serve them).
  * ws_version() returns the library's value: compare it with the header's before calling anything else. */
-#define WS_VERSION 108
+#define WS_VERSION 109
 WS_API int ws_version(void);
 WS_API const char* ws_last_error(void);
 /* Number of fbank frames for num_samples at snip_edges=True (25 ms / 10 ms):
@@ -276,6 +277,19 @@ WS_API int ws_debug_clock_probe(uint64_t* out, int samples, int64_t period_ticks
  * outputs are the specialised kernel's bits, which is how the tests pin it.  Returns 0, or WS_ERR_INVALID_ARG for an
  * unknown mode. */
 WS_API int ws_debug_fbank_mode(int mode);
+/* ERes2Net's attentional feature fusion (wespeaker/models/eres2net.py:75-103) as the engine runs it, on caller-supplied
+ * DEVICE buffers (tests/test_gpu_aff_fuse.py): per row m of channels-last tensors
+ *   h = silu(w1 [x[m] | y[m]] + b1),  a = 1 + tanh(w2 h + b2),  out[m] = x[m] * a + y[m] * (2 - a)
+ * w1 float32[channels / 4][2 * channels], b1 [channels / 4], w2 [channels][channels / 4], b2 [channels]: the two 1x1
+ * convolutions with their biases and eval BatchNorms already folded in.  x / y / out: a pointer, a row stride and a
+ * channel offset in floats each (multiples of 4; a channel slice of a wider row is fine), `rows` rows; out shares no
+ * element with x or y.  channels: a multiple of 32 in [64, 2048].  row_len (DEVICE int32[rows / image_pixels], or NULL):
+ * rows are images of image_pixels pixels in lines of image_width, and pixels whose column is >= row_len[image] are
+ * stored as exact zeros whatever the inputs hold there (ragged batches).  WS_ERR_INVALID_ARG with the reason in
+ * ws_last_error for anything outside that contract; nothing is launched then. */
+WS_API int ws_debug_aff_fuse(const float* x, int ldx, int x_off, const float* y, int ldy, int y_off, float* out, int ldo,
+                             int o_off, const float* w1, const float* b1, const float* w2, const float* b2, int rows,
+                             int channels, const int32_t* row_len, int image_pixels, int image_width, ws_stream stream);
 /* Read-only tap on the activations a forward leaves in the engine's workspace (no reference counterpart; the per-layer
  * parity tests of tests/test_gpu_layers.py).  A stream-ordered device-to-device copy of the named fp32 tensor as the
  * LAST chunk of the LAST forward on this engine left it (a batch beyond max_batch runs in chunks: the tap holds the
@@ -297,6 +311,9 @@ WS_API int ws_debug_fbank_mode(int mode);
  * SimAM-ResNet names: block (the gated result), mid (conv1's output), sc (the downsample convolution's output), and
  * after a full forward hid (B * T', 128: the first attention layer), logits (B * T', D; D in f * C + c order),
  * pooled (B, 2D); block1 = a copy of the first block's output made during the forward.
+ * ERes2Net names (tests/test_gpu_eres2net.py): stem (stopped at 0); of the last executed block: block, mid (conv1's
+ * output, width * scale channels), cat (the concat conv3 reads), sc; after a full forward fuse12 / fuse123 / fuse1234
+ * (the global fusions, rows = B * H * W of their level), pooled, and emb_a for two-embedding models.
  * CAM++ names (tests/test_gpu_campplus_layers.py).  The FCM head rotates three buffers and the trunk ping-pongs two, so
  * a stop point (ws_debug_engine_stop_after, stages 0 .. 9) selects what is read:
  *   stem     the stem's output, [b][f][t][32] as rows = B * F * T      -- only when stopped at 0

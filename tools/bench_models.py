@@ -18,6 +18,9 @@ CASES = [  # (model, embed_dim, batch, chunk)
     ("ResNet34", 256, 512, 512),
     ("ResNet221", 256, 128, 64),
     ("CAMPPlus", 512, 512, 512),                   # its GEMMs have M = B*T/2 rows: batch 512 fills the chip
+    ("ERes2Net34_Base", 512, 256, 256),            # the hub's eres2net asset (embed 512: the recipes' value)
+    ("ERes2Net34_Large", 512, 128, 128),
+    ("ERes2Net34_aug", 512, 64, 64),
 ]
 
 def main():

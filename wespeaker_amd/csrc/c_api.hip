@@ -263,6 +263,7 @@ int ws_engine_create(const char* model_name, int feat_dim, int embed_dim, int de
   if (!m) m = make_resnet(model_name, feat_dim, embed_dim);
   if (!m) m = make_campplus(model_name, feat_dim, embed_dim);
   if (!m) m = make_samresnet(model_name, feat_dim, embed_dim);
+  if (!m) m = make_eres2net(model_name, feat_dim, embed_dim);
   if (!m) {
     set_error("ws_engine_create: unknown model '%s'", model_name);
     return WS_ERR_UNKNOWN_MODEL;
@@ -714,6 +715,26 @@ int ws_debug_fbank_mode(int mode) {
     return WS_ERR_INVALID_ARG;
   }
   set_fbank_debug_mode(mode);
+  return WS_OK;
+}
+
+int ws_debug_aff_fuse(const float* x, int ldx, int x_off, const float* y, int ldy, int y_off, float* out, int ldo,
+                      int o_off, const float* w1, const float* b1, const float* w2, const float* b2, int rows, int channels,
+                      const int32_t* row_len, int image_pixels, int image_width, ws_stream stream) {
+  AffFuseParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.x = x; p.ldx = ldx; p.x_off = x_off;
+  p.y = y; p.ldy = ldy; p.y_off = y_off;
+  p.out = out; p.ldo = ldo; p.o_off = o_off;
+  p.W1 = w1; p.ldw1 = 2 * channels; p.b1 = b1;
+  p.W2 = w2; p.ldw2 = channels / 4; p.b2 = b2;
+  p.M = rows; p.C = channels;
+  p.row_len = row_len; p.HW = image_pixels; p.W = image_width;
+  if (const char* why = aff_fuse_refusal(p)) {        // nothing is launched
+    set_error("ws_debug_aff_fuse: %s (rows %d, channels %d)", why, rows, channels);
+    return WS_ERR_INVALID_ARG;
+  }
+  WS_HIP_CHECK(launch_aff_fuse(p, (hipStream_t)stream));
   return WS_OK;
 }
 

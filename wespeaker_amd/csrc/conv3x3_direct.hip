@@ -380,7 +380,7 @@ bool conv3x3_direct_f32_supported(const ConvGemmParams& p) {
          p.stride_w == 1 && (p.stride_h == 1 || p.stride_h == 2) &&
          !p.residual16 && !p.colsum && !p.colsumsq && !p.pool_partial &&
          !p.seg_scale && !p.post_scale && !p.bias_img && !p.D2 && p.splitk <= 1 && p.m_begin == 0 &&
-         p.act != ACT_TANH && (!p.residual || ((p.ldr & 3) == 0 && (p.r_off & 3) == 0)) &&
+         (p.act == ACT_NONE || p.act == ACT_RELU) && (!p.residual || ((p.ldr & 3) == 0 && (p.r_off & 3) == 0)) &&
          (long long)p.M * 32 >= (1 << 22);       // small maps stay on the tile kernels (persistent patches need work)
 }
 
@@ -428,7 +428,7 @@ bool conv3x3_direct_supported(const ConvGemmParams& p) {
          (p.stride_h == 1 || p.stride_h == 2) && (p.stride_w == 1 || p.stride_w == 2) &&
          !(p.stride_h == 1 && p.stride_w == 2) && !p.residual && !p.colsum && !p.pool_partial &&
          !p.seg_scale && !p.post_scale && !p.bias_img && !p.D2 && p.splitk <= 1 && p.m_begin == 0 &&
-         p.act != ACT_TANH && (!p.residual16 || (p.ldr == p.N && p.r_off == 0));
+         (p.act == ACT_NONE || p.act == ACT_RELU) && (!p.residual16 || (p.ldr == p.N && p.r_off == 0));
 }
 
 template <int C, int SH, int SW>

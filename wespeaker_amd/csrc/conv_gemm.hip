@@ -74,11 +74,12 @@ void dispatch_log_note(const ConvGemmParams& p, const char* kernel) {
   // the problem as the dispatcher sees it: rows of this launch, N, K, taps / strides, back-end, operand forms,
   // fused extras
   snprintf(key, sizeof(key),
-           "rows=%d N=%d K=%d k=%dx%d s=%dx%d d=%dx%d prec=%d A=%s out=%s%s%s%s%s%s%s%s%s -> %s",
+           "rows=%d N=%d K=%d k=%dx%d s=%dx%d d=%dx%d prec=%d A=%s out=%s%s%s%s%s%s%s%s%s%s -> %s",
            p.M - p.m_begin, p.N, p.K, p.kh, p.kw, p.stride_h, p.stride_w, p.dil_h, p.dil_w, p.prec,
            p.A16 ? "f16" : "f32", p.D ? "f32" : "", p.D16 ? "f16" : "", p.A2 ? " +A2" : "",
            p.pre_scale ? " +pre" : "", p.residual || p.residual16 ? " +res" : "", p.colsum ? " +colsum" : "",
-           p.pool_partial ? " +pool" : "", p.splitk > 1 ? " +splitk" : "", p.row_len ? " +mask" : "", kernel);
+           p.pool_partial ? " +pool" : "", p.splitk > 1 ? " +splitk" : "", p.row_len ? " +mask" : "",
+           p.act == ACT_RELU20 ? " +relu20" : "", kernel);     // (the clamp alone is named: the older tables stay as they are)
   std::lock_guard<std::mutex> lk(g_dlog_mu);
   ++g_dlog[key];
 }
@@ -363,6 +364,9 @@ __device__ __forceinline__ void gemm_epilogue(const ConvGemmParams& p,
             } else if (p.act == ACT_TANH) {
 #pragma unroll
               for (int q = 0; q < 4; ++q) v[q] = tanhf(v[q]);
+            } else if (p.act == ACT_RELU20) {
+#pragma unroll
+              for (int q = 0; q < 4; ++q) v[q] = relu20_f(v[q]);
             }
             if (p.post_scale) v = v * ps + pb;
             store_row(m, v);
@@ -439,6 +443,9 @@ __device__ __forceinline__ void gemm_epilogue(const ConvGemmParams& p,
             } else if (p.act == ACT_TANH) {
 #pragma unroll
               for (int q = 0; q < 4; ++q) v[q] = tanhf(v[q]);
+            } else if (p.act == ACT_RELU20) {
+#pragma unroll
+              for (int q = 0; q < 4; ++q) v[q] = relu20_f(v[q]);
             }
             if (p.post_scale) v = v * ps + pb;
             if (ROWOPS && p.seg_scale) v *= ss[g];
@@ -1974,7 +1981,7 @@ static hipError_t launch_prec(const ConvGemmParams& p, hipStream_t stream) {
   if (big < 0) { const char* ev = getenv("WS_BIG_TILES"); big = ev ? atoi(ev) : 3; }
   if (g_ws_epi16 < 0) g_ws_epi16 = 1;                         // (tools/gemm_probe sets it to 0 for its A/B)
   // D16-only layers finish through the binary16 one-phase epilogue (g_ws_epi16 = 0: the fp32 two-phase one)
-  const bool epi16_ok = g_ws_epi16 && big >= 2 && p.D16 && !p.D && !p.D2 && p.act != ACT_TANH && (p.ldd16 & 7) == 0 &&
+  const bool epi16_ok = g_ws_epi16 && big >= 2 && p.D16 && !p.D && !p.D2 && (p.act == ACT_NONE || p.act == ACT_RELU) && (p.ldd16 & 7) == 0 &&
                         (p.d_off & 7) == 0 && (!p.colsum || p.Hout * p.Wout >= 64);
   // (the row mask of ragged batches lives in that binary16 epilogue only -- the fp32 quadrant epilogue has no row
   // operands -- and is written for H = 1; other masked layers stay on the 128x128 kernels)
@@ -2092,6 +2099,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvGemmParams
   if (p.residual) v += p.residual[(long long)m * p.ldr + p.r_off + n];
   if (p.act == ACT_RELU) v = relu_f(v);
   else if (p.act == ACT_TANH) v = tanhf(v);
+  else if (p.act == ACT_RELU20) v = relu20_f(v);
   if (p.post_scale) v = v * p.post_scale[n] + p.post_shift[n];
   p.D[(long long)m * p.ldd + p.d_off + n] = v;
   if (p.D2 && n >= p.d2_col0) p.D2[(long long)m * p.ldd2 + p.d2_off + (n - p.d2_col0)] = v;

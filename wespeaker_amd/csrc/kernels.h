@@ -39,7 +39,7 @@ inline hipError_t ensure_dynamic_lds(const void* kernel, size_t bytes, size_t (&
 }
 
 
-enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
+enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_RELU20 = 3 };
 
 // ReLU with torch.relu's treatment of non-finite values: NaN stays NaN, +inf stays +inf (bit-identical
 // to fmaxf(v, 0) on finite input).  fmaxf returns the non-NaN operand, i.e. it would turn the NaN that a
@@ -47,6 +47,9 @@ enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
 // reach the embedding as a finite wrong number; with this form it arrives as NaN and
 // ws_engine_check_range reports it.
 __device__ __forceinline__ float relu_f(float v) { return v < 0.f ? 0.f : v; }
+// ACT_RELU20: ERes2Net's clamped ReLU, Hardtanh(0, 20) (eres2net.py:44-52); NaN stays NaN like relu_f's.  A kernel of
+// the conv-GEMM family either applies it or declines the problem in its *_supported / dispatch predicate.
+__device__ __forceinline__ float relu20_f(float v) { return v < 0.f ? 0.f : (v > 20.f ? 20.f : v); }
 
 
 // Implicit-GEMM convolution / linear layer on channels-last activations:
@@ -277,6 +280,25 @@ hipError_t launch_simam_residual_relu(const float* y, const float* res, int ldr,
 // (variance clamped at 1e-5) of x[(b*F + f)*T + t][c] -> pooled[b] = [mean(D) | std(D)], D index c*F + f
 hipError_t launch_asp_pool(const float* x, const float* e, int B, int F, int T, int C, float* pooled,
                            hipStream_t stream, const int* lens = nullptr);
+// ---- ERes2Net (aff_fuse.hip)
+// Attentional feature fusion (eres2net.py:75-103) in one launch over channels-last rows (fp32, exact-fp32 MFMA):
+//   h = silu(W1 [x[m] | y[m]] + b1),  a = 1 + tanh(W2 h + b2),  out[m] = x[m] * a + y[m] * (2 - a)
+// W1: [C/4][ldw1 >= 2C] and W2: [C][ldw2 >= C/4], with the 1x1 convolutions' biases and eval BatchNorms folded in (float64, host).
+// x / y / out: a pointer, a row stride and a channel offset each (a channel slice of a wider row is fine); out shares
+// no element with x or y.  C % 32 == 0, 64 <= C <= 2048; M arbitrary.  row_len (optional, as ConvGemmParams::row_len):
+// [M / HW] valid widths of images of HW pixels, W per line; pixels with ox >= row_len[img] are stored as exact zeros.
+struct AffFuseParams {
+  const float* x; int ldx, x_off;
+  const float* y; int ldy, y_off;
+  float* out; int ldo, o_off;
+  const float* W1; int ldw1; const float* b1;
+  const float* W2; int ldw2; const float* b2;
+  int M, C;
+  const int* row_len; int HW, W;
+};
+bool aff_fuse_supported(const AffFuseParams& p);
+const char* aff_fuse_refusal(const AffFuseParams& p);      // what aff_fuse_supported objects to (null: nothing)
+hipError_t launch_aff_fuse(const AffFuseParams& p, hipStream_t stream);
 // CAM++ context (campplus.py:108-135): ctx = mean_T(h) + segmean_100(h); m = sigmoid(W2 relu(W1 ctx + b1) + b2)
 // h: [B*T][C] (C = 128); mask out: [B][segs][Cout]
 hipError_t launch_cam_context_from_colsum(const float* colsum, int B, int T, int C, const float* w1,

@@ -71,6 +71,7 @@ __global__ __launch_bounds__(64 * NW) void small_m_gemm_f32_kernel(const ConvGem
     float v = acc[r] + b;
     if (p.act == ACT_RELU) v = relu_f(v);
     else if (p.act == ACT_TANH) v = tanhf(v);
+    else if (p.act == ACT_RELU20) v = relu20_f(v);
     if (p.post_scale) v = v * sc + sh;
     p.D[(long long)m * p.ldd + p.d_off + n] = v;
   }

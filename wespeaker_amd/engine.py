@@ -21,9 +21,10 @@ WINDOW_TYPES = {"hamming": 0, "povey": 1}
 
 SUPPORTED_MODELS = ("ECAPA_TDNN_c512", "ECAPA_TDNN_GLOB_c512", "ECAPA_TDNN_c1024",
                     "ECAPA_TDNN_GLOB_c1024", "ResNet18", "ResNet34", "ResNet50", "ResNet101",
-                    "ResNet152", "ResNet221", "ResNet293", "CAMPPlus", "SimAM_ResNet34_ASP", "SimAM_ResNet100_ASP")
+                    "ResNet152", "ResNet221", "ResNet293", "CAMPPlus", "SimAM_ResNet34_ASP", "SimAM_ResNet100_ASP",
+                    "ERes2Net34_Base", "ERes2Net34_Large", "ERes2Net34_aug")
 
-DEFAULT_EMBED_DIM = {"ECAPA": 192, "ResNe": 256, "CAMPP": 512, "SimAM": 256}
+DEFAULT_EMBED_DIM = {"ECAPA": 192, "ResNe": 256, "CAMPP": 512, "SimAM": 256, "ERes2": 512}
 
 
 def simam_model_args(state_dict, feat_dim, model_args):
@@ -277,6 +278,10 @@ class NativeSpeakerModel:
     # its transit); stem / block / mid / sc / fcm = FCM maps (B*F*T, 32), tdnn / dense / transit / h = (B*T', cols),
     # mask = (B*segments, 32); h and mask only where the three-launch dense path ran; pooled after a full forward
     CAMPPLUS_TAP_NAMES = ("stem", "block", "mid", "sc", "fcm", "tdnn", "dense", "transit", "h", "mask", "pooled")
+    # ERes2Net34_*: stem (stopped at 0); block / mid (conv1's output, width * scale) / cat (the concat conv3 reads) / sc of
+    # the last executed block (stop_after 1..16); fuse12 / fuse123 / fuse1234 (the global fusions, (B*H*W, C) of their
+    # level), pooled and -- two_emb_layer -- emb_a after a full forward
+    ERES2NET_TAP_NAMES = ("stem", "block", "mid", "cat", "sc", "fuse12", "fuse123", "fuse1234", "pooled", "emb_a")
 
     def stop_after(self, n_blocks):
         """Diagnostic (ResNet / SimAM-ResNet / CAMPPlus; ws_debug_engine_stop_after): every later forward returns after
@@ -297,7 +302,7 @@ class NativeSpeakerModel:
 
     def tap_shape(self, name):
         """(rows, cols) of a tap without copying it (ws_debug_engine_tap with a NULL destination).  Names: TAP_NAMES
-        (ECAPA-TDNN), RESNET_TAP_NAMES, SIMAM_TAP_NAMES, CAMPPLUS_TAP_NAMES."""
+        (ECAPA-TDNN), RESNET_TAP_NAMES, SIMAM_TAP_NAMES, CAMPPLUS_TAP_NAMES, ERES2NET_TAP_NAMES."""
         rows, cols = ctypes.c_int32(0), ctypes.c_int32(0)
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().ws_debug_engine_tap(self._h, name.encode(), None, 0, ctypes.byref(rows),
@@ -384,10 +389,10 @@ class NativeSpeakerModel:
         """Return convention of the reference modules (callers use `outputs[-1] if tuple`):
         ECAPA -> (out4, embed) (ecapa_tdnn.py:227-234), ResNet -> (tensor(0.0), embed_a) or
         (embed_a, embed_b) (resnet.py:192-204), CAM++ -> tensor (campplus.py:409-413), SimAM_ResNet*_ASP -> tensor
-        (samresnet.py:142-149).  The leading element is not materialised on this path (None for ECAPA / two-layer
+        (samresnet.py:142-149), ERes2Net34_* -> tensor (eres2net.py:380-391).  The leading element is not materialised on this path (None for ECAPA / two-layer
         ResNet)."""
         emb = self.embed(feats)
-        if self.model_name.startswith(("CAMPPlus", "SimAM_ResNet")):
+        if self.model_name.startswith(("CAMPPlus", "SimAM_ResNet", "ERes2Net")):
             return emb
         if self.model_name.startswith("ResNet"):
             return torch.tensor(0.0), emb
