@@ -14,6 +14,8 @@ where the reference is present, by a live comparison (tests/test_eres2net_cpu.py
 `clamp` and `swap_aff` exist for the fixtures with teeth of the tests: clamp=False replaces Hardtanh(0, 20) by max(x, 0),
 swap_aff=True exchanges AFF's two arguments -- what an implementation with either mistake would compute.
 """
+import re
+
 import torch
 import torch.nn.functional as F
 
@@ -46,16 +48,26 @@ def aff(sd, p, x, y):
 
 @torch.no_grad()
 def eres2net_forward(sd, feats, name="ERes2Net34_Base", dtype=torch.float64, return_intermediates=False, clamp=True,
-                     swap_aff=False):
+                     swap_aff=False, override=None):
     """feats (B, T, F) -> embedding (B, E) in `dtype`.  return_intermediates: also a dict of (B, C, F, T) maps -- `stem`;
     for the i-th block (1-based) `b<i>.block`, `b<i>.mid` (conv1 + bn1 + relu), `b<i>.cat` (what conv3 reads), `b<i>.sc`
     where the block has a shortcut convolution; `fuse12`, `fuse123`, `fuse1234`; `pooled` (B, 2D); `emb_a` (two-layer
     models: relu + seg_bn_1 of seg_1's output, what seg_2 reads); and `aff` = a list of (prefix, x, y, out) per AFF in
-    execution order."""
+    execution order.  override = {`b<i>.cat` / `b<i>.block`: (B, C, F, T) tensor}: that intermediate is replaced where it
+    is recorded and the forward's own tail runs on it (the fixtures with teeth of tests/test_gpu_eres2net_layers.py)."""
     m, base_width, scale, exp = LAYOUTS[name]
     sd = _cast(sd, dtype)
     act = (lambda t: t.clamp(0.0, 20.0)) if clamp else (lambda t: t.clamp(min=0.0))
     mid = {"aff": []}
+    override = {k: torch.as_tensor(v).to(dtype) for k, v in (override or {}).items()}
+    unknown = [k for k in override if not re.fullmatch(r"b([1-9]|1[0-6])\.(cat|block)", k)]
+    assert not unknown, unknown
+
+    def replaced(key, own):
+        if key not in override:
+            return own
+        assert override[key].shape == own.shape, (key, tuple(override[key].shape), tuple(own.shape))
+        return override[key]
 
     def fuse(p, x, y):
         out = aff(sd, p, y, x) if swap_aff else aff(sd, p, x, y)
@@ -89,13 +101,13 @@ def eres2net_forward(sd, feats, name="ERes2Net34_Base", dtype=torch.float64, ret
                     sp = fuse(p + ".fuse_models.%d" % (j - 1), sp, spx[j])
                     sp = act(_conv_bn(sd, p + ".convs.%d" % (j - 1), p + ".bns.%d" % (j - 1), sp, padding=1))
                     cat.append(sp)
-            cat = torch.cat(cat, 1)
+            cat = replaced("b%d.cat" % i, torch.cat(cat, 1))
             y3 = _conv_bn(sd, p + ".conv3", p + ".bn3", cat)
             res = out
             if p + ".shortcut.0.weight" in sd:
                 res = _conv_bn(sd, p + ".shortcut.0", p + ".shortcut.1", out, stride=stride)
                 mid["b%d.sc" % i] = res
-            out = act(y3 + res)
+            out = replaced("b%d.block" % i, act(y3 + res))
             mid["b%d.mid" % i], mid["b%d.cat" % i], mid["b%d.block" % i] = y1, cat, out
         stage_out.append(out)
     prev = stage_out[0]
