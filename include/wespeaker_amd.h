@@ -64,9 +64,11 @@ typedef void* ws_stream;                /* hipStream_t */
  * `cmn` flags now mean "apply the frontend's CMVN"; 105: ws_forward_ragged_cmvn added; 106: ws_debug_engine_tap added;
  * 107: ws_debug_engine_stop_after added; 108: ws_debug_engine_stop_after and ws_debug_engine_tap serve CAM++ -- a
  * caller that relied on their refusing that family sees other results; 109: ws_debug_aff_fuse added, ws_engine_create
- * knows the ERes2Net34 names, ws_debug_engine_tap / ws_debug_engine_stop_after serve them).
+ * knows the ERes2Net34 names, ws_debug_engine_tap / ws_debug_engine_stop_after serve them; 110:
+ * ws_debug_engine_stop_after serves ECAPA-TDNN (1 .. 3) and ws_debug_engine_tap reads its binary16 tensors -- a caller
+ * that relied on the refusals sees other results).
  * ws_version() returns the library's value: compare it with the header's before calling anything else. */
-#define WS_VERSION 109
+#define WS_VERSION 110
 WS_API int ws_version(void);
 WS_API const char* ws_last_error(void);
 /* Number of fbank frames for num_samples at snip_edges=True (25 ms / 10 ms):
@@ -296,8 +298,16 @@ WS_API int ws_debug_aff_fuse(const float* x, int ldx, int x_off, const float* y,
  * utterances of the last one).  ECAPA-TDNN names, workspace layout, channels contiguous:
  *   frame level, rows = B * T_slot:  out1 (C)  cat = out2 | out3 | out4 (3C)  h (1536)
  *                                    y1, y2, y3 (C): conv1 / Res2 / conv3 output of the last block (layer4), before SE
+ *                                    att (128): linear1 + tanh of the pooling, where astp_fused_kernel did not run
  *   utterance level, rows = B:       se_s (C, layer4's gate)  stats = [mean; std] (3072, GLOB models)
  *                                    bias_img (128, GLOB models)  pooled (3072)
+ *   binary16 tensors of WS_PREC_F16, widened exactly to fp32 (the plain names stay the fp32 tensors, or an error where
+ *   the back-end keeps none -- both exist together for T < 64):
+ *                                    out1_16 (C)  cat16 (3C)  h16 (1536)  att16 (128)  y2_16 (C)
+ *                                    y3_16 (C, T >= 64 only)  col16 (layer 1's im2col image, 5 * F rounded up to 64)
+ *   after a stop point (ws_debug_engine_stop_after, 1 .. 3) y1 / y2 / y3 / se_s and their binary16 forms are those of
+ *   THAT block, cat / cat16 hold the block outputs up to it (the later columns are stale), and h, att, stats,
+ *   bias_img, pooled are refused.
  * ResNet names (tests/test_gpu_resnet_layers.py), maps in the layout [b][f][t][c] as rows = B * H * W, cols = C.  The
  * model rotates four activation buffers, so only the LAST EXECUTED block's tensors survive a forward: set a stop point
  * (ws_debug_engine_stop_after) to read an earlier block.
@@ -341,15 +351,16 @@ WS_API int ws_debug_aff_fuse(const float* x, int ldx, int x_off, const float* y,
  * the last chunk. */
 WS_API int ws_debug_engine_tap(ws_engine* eng, const char* name, float* dst, int64_t cap_floats, int32_t* rows,
                                int32_t* cols, ws_stream stream);
-/* Debug stop point of the 2-D families and CAM++ (ResNet, SimAM-ResNet, CAMPPlus; no reference counterpart): every later forward on this
+/* Debug stop point (ResNet, SimAM-ResNet, ERes2Net, CAMPPlus, ECAPA-TDNN; no reference counterpart): every later forward on this
  * engine returns after the stem (n_blocks = 0) or after the last launch of the n-th residual block (a fused
  * conv3 + next-conv1 launch belongs to block n), so that ws_debug_engine_tap can read what those launches left.
  * Pooling and the head do not run; the embedding output is zero-filled on the stream.  -1 (the default) = the full
  * forward: with it no launch, store or dispatch decision differs from a library without the stop point (one host-side
  * integer, tested once per block).  CAM++ counts stages instead of residual blocks: 0 = the stem, 1 .. 4 = the FCM
- * residual blocks, 5 = head.conv2, 6 = the TDNN layer, 7 / 8 / 9 = dense block 1 / 2 / 3 AND its transit.
- * WS_ERR_INVALID_ARG: n_blocks < -1 or beyond the model's block / stage count; a family without a block loop
- * (ECAPA-TDNN); an engine that is not finalized. */
+ * residual blocks, 5 = head.conv2, 6 = the TDNN layer, 7 / 8 / 9 = dense block 1 / 2 / 3 AND its transit.  ECAPA-TDNN
+ * takes 1, 2 or 3: return after that SE-Res2 block (its SE scale + residual launch), layer 1 has no stop of its own.
+ * WS_ERR_INVALID_ARG: n_blocks < -1 or beyond the model's block / stage count (ECAPA-TDNN: 0 as well); an engine that
+ * is not finalized. */
 WS_API int ws_debug_engine_stop_after(ws_engine* eng, int n_blocks);
 /* Algorithmic FLOPs (2 x MACs of every conv/linear) of one forward at (batch, num_frames). */
 WS_API double ws_engine_flops(const ws_engine* eng, int batch, int num_frames);

@@ -602,7 +602,9 @@ def test_stop_and_tap_api_edges():
     model.reserve(2, 100)                         # re-sizing the workspace forgets the last chunk
     with pytest.raises(NativeError, match="no forward"):
         model.tap("block")
-    # a family without a block loop
+    # ECAPA-TDNN stops after its SE-Res2 blocks 1 .. 3 only (tests/test_gpu_f16_layers.py reads them)
     from test_gpu_layers import _engine as ecapa_engine
-    with pytest.raises(NativeError, match="no residual-block loop"):
-        ecapa_engine("ECAPA_TDNN_c512").stop_after(1)
+    for n in (0, 4):
+        with pytest.raises(NativeError, match="1, 2 or 3"):
+            ecapa_engine("ECAPA_TDNN_c512").stop_after(n)
+    ecapa_engine("ECAPA_TDNN_c512").stop_after(2).stop_after(-1)

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("WS_LIB_PATH") or os.path.join(_HERE, "lib", "libwespe
 
 _lib = None
 
-ABI_VERSION = 109      # = WS_VERSION of include/wespeaker_amd.h
+ABI_VERSION = 110      # = WS_VERSION of include/wespeaker_amd.h
 
 # name -> (restype, argtypes); also used by the ABI test to check every header symbol is exported
 SIGNATURES = {

@@ -213,8 +213,9 @@ struct Model {
     return WS_ERR_INVALID_ARG;
   }
   // ws_debug_engine_stop_after: the 2-D families (ResNet, SimAM-ResNet) return from forward_chunk after the stem
-  // (0) or after the n-th residual block, CAM++ after stage n (campplus_model.hip), with the embedding zero-filled;
-  // -1 = the full forward.  Families without a block loop keep this default.
+  // (0) or after the n-th residual block, CAM++ after stage n (campplus_model.hip), ECAPA-TDNN after SE-Res2 block
+  // 1 .. 3 (ecapa_model.hip), with the embedding zero-filled; -1 = the full forward.  Families without a block loop
+  // keep this default.
   virtual int set_stop_after(int n_blocks) {
     set_error("ws_debug_engine_stop_after: this model family has no residual-block loop to stop in (n_blocks = %d; "
               "ResNet and SimAM-ResNet have one, CAM++ has stages)", n_blocks);

@@ -177,7 +177,10 @@ struct EcapaModel : ModelBase {
       p0.row_len = L0;
       WS_LAUNCH(gemm(p0, st, 5 * feat_dim));
     }
+    const bool col16_used = f16io && layer1.ldw <= 512 && feat_dim % 4 == 0;
     for (int L = 0; L < 3; ++L) {
+      // debug stop point (ws_debug_engine_stop_after; -1 in production: one host-side comparison per block)
+      if (stop_after == L && L > 0) return end_stopped(L, B, T, f16io, allf16, col16_used, emb, st);
       const int d = L + 2;
       const float* x = L == 0 ? out1 : cat;
       const int ldx = L == 0 ? C : 3 * C;
@@ -265,11 +268,13 @@ struct EcapaModel : ModelBase {
                                         f16io ? cat16 : nullptr);
       }));
     }
+    if (stop_after == 3) return end_stopped(3, B, T, f16io, allf16, col16_used, emb, st);
     // cat -> Conv1d(3C -> 1536, k1) -> ReLU
     // (GLOB, T >= 64: the epilogue also leaves per-tile column sums of h for the context statistics)
     const bool stats_from_colsum = glob && T >= 64;
     const bool stats_from_sums = stats_from_colsum && gemm_precision == 0 && !L0;
     const bool h_half = allf16;
+    bool att_left = true;                      // (taps: the fused pooling kernel keeps linear1's output on the chip)
     {
       ConvGemmParams pc = conv1d(catconv, cat, 3 * C, 0, h, 1536, 0, B, T, 1, ACT_RELU);
       if (stats_from_colsum) pc.colsum = colsum;
@@ -318,6 +323,7 @@ struct EcapaModel : ModelBase {
                                         e);       // (e: the logits buffer of the unfused path, free here: segment tuples)
       prof.end(st);
       WS_LAUNCH(fe);
+      att_left = false;
     } else {
     WS_LAUNCH(gemm(a1, st));
     if (T >= 64) {
@@ -344,10 +350,34 @@ struct EcapaModel : ModelBase {
     last_chunk.B = B; last_chunk.T = T; last_chunk.prec = gemm_precision;
     last_chunk.chain_half = allf16;
     last_chunk.y2_half = f16io && res2_half_out_supported(w, T, 4);
+    last_chunk.f16io = f16io; last_chunk.col16 = col16_used; last_chunk.att = att_left; last_chunk.blocks = 3;
+    last_chunk.full = true;
     return 0;
   }
 
-  // ws_debug_engine_tap: the fp32 tensors forward_chunk leaves behind (layout: reserve(); [rows][cols] contiguous)
+  // a chunk stopped after SE-Res2 block n (1 .. 3): what the taps may read, and a zero embedding
+  int end_stopped(int n, int B, int T, bool f16io, bool allf16, bool col16_used, float* emb, hipStream_t st) {
+    if (int r = stop_chunk(emb, B, st)) return r;
+    last_chunk.B = B; last_chunk.T = T; last_chunk.prec = gemm_precision;
+    last_chunk.chain_half = allf16;
+    last_chunk.y2_half = f16io && res2_half_out_supported(w, T, n + 1);
+    last_chunk.f16io = f16io; last_chunk.col16 = col16_used; last_chunk.att = false; last_chunk.blocks = n;
+    last_chunk.full = false;
+    return 0;
+  }
+
+  int set_stop_after(int n) override {
+    if (n != -1 && (n < 1 || n > 3)) {
+      set_error("ws_debug_engine_stop_after: n_blocks = %d, %s has 3 SE-Res2 blocks: 1, 2 or 3 (-1 = the full forward)",
+                n, name.c_str());
+      return WS_ERR_INVALID_ARG;
+    }
+    stop_after = n;
+    return WS_OK;
+  }
+
+  // ws_debug_engine_tap: the tensors forward_chunk leaves behind (layout: reserve(); [rows][cols] contiguous).  The plain
+  // names are the fp32 tensors; the *16 names are the binary16 tensors of the f16 back-end, widened exactly.
   int tap(const char* name, float* dst, int64_t cap_floats, int32_t* rows, int32_t* cols, hipStream_t st) override {
     const LastChunk& lc = last_chunk;
     if (lc.B <= 0) {
@@ -355,24 +385,45 @@ struct EcapaModel : ModelBase {
       return WS_ERR_INVALID_ARG;
     }
     const int M = lc.B * lc.T;
-    const char* half = "the f16 back-end with T >= 64 keeps it in binary16 only";
+    const char* half = "the f16 back-end with T >= 64 keeps it in binary16 only: read the name with the suffix 16";
     const char* noglob = "only the GLOB models compute the context statistics";
+    const char* nof16 = "only the f16 back-end writes the binary16 tensors";
+    const char* stopped = "the forward was stopped after an SE-Res2 block: pooling and the head did not run";
+    const bool full = lc.full;
     const std::string n = name;
     if (n == "out1") return tap_copy(name, lc.chain_half ? nullptr : out1, half, M, C, dst, cap_floats, rows, cols, st);
     if (n == "cat") return tap_copy(name, lc.chain_half ? nullptr : cat, half, M, 3 * C, dst, cap_floats, rows, cols, st);
-    if (n == "h") return tap_copy(name, lc.chain_half ? nullptr : h, half, M, 1536, dst, cap_floats, rows, cols, st);
     if (n == "y1") return tap_copy(name, y1, "", M, C, dst, cap_floats, rows, cols, st);
-    if (n == "y2") return tap_copy(name, lc.y2_half ? nullptr : y2, "the f16 back-end's fused Res2 chain stores binary16 only",
+    if (n == "y2") return tap_copy(name, lc.y2_half ? nullptr : y2,
+                                   "the f16 back-end's fused Res2 chain stores binary16 only: read y2_16",
                                    M, C, dst, cap_floats, rows, cols, st);
     if (n == "y3") return tap_copy(name, lc.chain_half ? nullptr : y3, half, M, C, dst, cap_floats, rows, cols, st);
     if (n == "se_s") return tap_copy(name, se_s, "", lc.B, C, dst, cap_floats, rows, cols, st);
+    // the binary16 tensors (col16: layer 1's im2col image, K padded to a multiple of 64 with zeros)
+    if (n == "col16") return tap_copy16(name, lc.col16 ? col16 : nullptr, nof16, M, layer1.ldw, dst, cap_floats, rows, cols, st);
+    if (n == "out1_16") return tap_copy16(name, lc.f16io ? out1_16 : nullptr, nof16, M, C, dst, cap_floats, rows, cols, st);
+    if (n == "cat16") return tap_copy16(name, lc.f16io ? cat16 : nullptr, nof16, M, 3 * C, dst, cap_floats, rows, cols, st);
+    if (n == "y2_16") return tap_copy16(name, lc.y2_half ? y2_16 : nullptr, nof16, M, C, dst, cap_floats, rows, cols, st);
+    if (n == "y3_16") return tap_copy16(name, lc.chain_half ? y3_16 : nullptr,
+                                        "only the f16 back-end with T >= 64 stores conv3's output in binary16", M, C, dst,
+                                        cap_floats, rows, cols, st);
+    if (!full) {
+      static const char* tail[] = {"h", "h16", "att", "att16", "stats", "bias_img", "pooled"};
+      for (auto t : tail)
+        if (n == t) return tap_copy(name, nullptr, stopped, 0, 0, dst, cap_floats, rows, cols, st);
+    }
+    if (n == "h") return tap_copy(name, lc.chain_half ? nullptr : h, half, M, 1536, dst, cap_floats, rows, cols, st);
+    if (n == "h16") return tap_copy16(name, lc.f16io ? h16 : nullptr, nof16, M, 1536, dst, cap_floats, rows, cols, st);
+    if (n == "att") return tap_copy(name, lc.att ? att : nullptr, "astp_fused_kernel keeps linear1's output on the chip",
+                                    M, 128, dst, cap_floats, rows, cols, st);
+    if (n == "att16") return tap_copy16(name, lc.f16io ? att16 : nullptr, nof16, M, 128, dst, cap_floats, rows, cols, st);
     if (n == "stats") return tap_copy(name, glob ? stats : nullptr, noglob, lc.B, 3072, dst, cap_floats, rows, cols, st);
     if (n == "bias_img") return tap_copy(name, glob ? bias_img : nullptr, noglob, lc.B, 128, dst, cap_floats, rows, cols, st);
     if (n == "pooled") return tap_copy(name, pooled, "", lc.B, 3072, dst, cap_floats, rows, cols, st);
-    set_error("ws_debug_engine_tap: unknown tensor '%s' (out1, cat, h, y1, y2, y3, se_s, stats, bias_img, pooled)", name);
+    set_error("ws_debug_engine_tap: unknown tensor '%s' (out1, cat, h, att, y1, y2, y3, se_s, stats, bias_img, pooled; "
+              "binary16: col16, out1_16, cat16, h16, att16, y2_16, y3_16)", name);
     return WS_ERR_INVALID_ARG;
   }
-
   double flops(int batch, int T) const override {
     double macs = 0;
     macs += (double)feat_dim * 5 * C;                       // layer1

@@ -13,6 +13,16 @@ namespace wsamd {
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
+// ws_debug_engine_tap on a tensor the f16 back-end keeps in binary16: widened to the fp32 destination, exactly (every
+// binary16 value is an fp32 value).  A template so that each translation unit that includes this header may hold it.
+template <int BLOCK = 256>
+__global__ __launch_bounds__(BLOCK) void tap_half_to_float_kernel(const uint16_t* __restrict__ src,
+                                                                  float* __restrict__ dst, long long n) {
+  const _Float16* s = reinterpret_cast<const _Float16*>(src);
+  for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * BLOCK)
+    dst[i] = (float)s[i];
+}
+
 struct ConvW {        // one conv / linear layer resident on the device
   size_t w = 0, b = 0, scale = 0, shift = 0;
   size_t wh = 0, wl = 0;    // hi / lo binary16 planes of w (same [N][ldw] layout), arena float offsets
@@ -88,6 +98,11 @@ struct ModelBase : Model {
     int B = 0, T = 0, prec = 0;
     bool chain_half = false;     // out1 / cat / y3 / h exist as binary16 only
     bool y2_half = false;        // the last block's Res2 output exists as binary16 only
+    bool f16io = false;          // the binary16 copies out1_16 / cat16 / h16 / att16 were written (f16 back-end)
+    bool col16 = false;          // ... and layer 1 ran on the binary16 im2col image
+    bool att = false;            // the unfused pooling path ran: linear1's fp32 output exists
+    int blocks = 3;              // ECAPA: SE-Res2 blocks the chunk executed
+    bool full = true;            // ... and it ran to its end (false: stopped there, ws_debug_engine_stop_after)
   } last_chunk;
   // ---- debug stop point of the 2-D families and CAM++ (ws_debug_engine_stop_after): -1 = the full forward, 0 = return
   // after the stem, n = after the n-th residual block (CAM++: after stage n).  The families with a block loop override
@@ -129,6 +144,29 @@ struct ModelBase : Model {
     } else {
       WS_HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
+    return WS_OK;
+  }
+  // the same for a binary16 workspace tensor (rows x cols halfs, contiguous): converted on the way, bit-exact
+  int tap_copy16(const char* name, const uint16_t* src, const char* why_absent, int rows_n, int cols_n, float* dst,
+                 int64_t cap_floats, int32_t* rows, int32_t* cols, hipStream_t st) {
+    if (!src) {
+      set_error("ws_debug_engine_tap: the last forward left no binary16 '%s' (%s)", name, why_absent);
+      return WS_ERR_INVALID_ARG;
+    }
+    if (rows) *rows = rows_n;
+    if (cols) *cols = cols_n;
+    if (!dst) return WS_OK;
+    const long long n = (long long)rows_n * cols_n;
+    if (cap_floats < n) {
+      set_error("ws_debug_engine_tap: '%s' is %d x %d floats, the destination holds %lld", name, rows_n, cols_n,
+                (long long)cap_floats);
+      return WS_ERR_CAPACITY;
+    }
+    if (n == 0) return WS_OK;
+    long long blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(tap_half_to_float_kernel<256>, dim3((unsigned)blocks), dim3(256), 0, st, src, dst, n);
+    WS_HIP_CHECK(hipGetLastError());
     return WS_OK;
   }
 

@@ -267,7 +267,11 @@ class NativeSpeakerModel:
                 _lib.check(_lib.lib().ws_engine_check_range(self._h, _lib.current_stream_ptr(self.device)),
                            "ws_engine_check_range")
 
-    TAP_NAMES = ("out1", "cat", "h", "y1", "y2", "y3", "se_s", "stats", "bias_img", "pooled")
+    TAP_NAMES = ("out1", "cat", "h", "y1", "y2", "y3", "se_s", "stats", "bias_img", "pooled", "att")
+    # ECAPA-TDNN, f16 back-end: the binary16 workspace tensors, widened exactly to fp32 (TAP_NAMES stay the fp32 tensors --
+    # for T >= 64 most of them do not exist then); col16 = layer 1's im2col image, y3_16 only for T >= 64.  After
+    # stop_after(1 .. 3): y1 / y2 / y3 / se_s (and *_16) of that block, cat / cat16 up to it; no h / att / stats / pooled
+    TAP_NAMES_F16 = ("col16", "out1_16", "cat16", "h16", "att16", "y2_16", "y3_16")
     # SimAM_ResNet*_ASP: block1 = a copy of the first block's output (B*F*T, in_planes); stem / block / mid / sc = the
     # last executed block's tensors (stop_after); hid / logits / pooled = the ASP head's, after a full forward
     SIMAM_TAP_NAMES = ("block1", "stem", "block", "mid", "sc", "hid", "logits", "pooled")
@@ -284,9 +288,10 @@ class NativeSpeakerModel:
     ERES2NET_TAP_NAMES = ("stem", "block", "mid", "cat", "sc", "fuse12", "fuse123", "fuse1234", "pooled", "emb_a")
 
     def stop_after(self, n_blocks):
-        """Diagnostic (ResNet / SimAM-ResNet / CAMPPlus; ws_debug_engine_stop_after): every later forward returns after
-        the stem (0) or after the n-th residual block (CAMPPlus: after stage n, see CAMPPLUS_TAP_NAMES), its embeddings
-        all zero, so that tap() reads that block's tensors.
+        """Diagnostic (ResNet / SimAM-ResNet / ERes2Net / CAMPPlus / ECAPA-TDNN; ws_debug_engine_stop_after): every later
+        forward returns after the stem (0) or after the n-th residual block (CAMPPlus: after stage n, see
+        CAMPPLUS_TAP_NAMES; ECAPA-TDNN: after SE-Res2 block 1, 2 or 3), its embeddings all zero, so that tap() reads that
+        block's tensors.
         -1 restores the full forward.  Prefer `with model.stopped_after(n): ...`, which always restores it."""
         _lib.check(_lib.lib().ws_debug_engine_stop_after(self._h, int(n_blocks)), "ws_debug_engine_stop_after")
         return self
@@ -301,8 +306,8 @@ class NativeSpeakerModel:
             self.stop_after(-1)
 
     def tap_shape(self, name):
-        """(rows, cols) of a tap without copying it (ws_debug_engine_tap with a NULL destination).  Names: TAP_NAMES
-        (ECAPA-TDNN), RESNET_TAP_NAMES, SIMAM_TAP_NAMES, CAMPPLUS_TAP_NAMES, ERES2NET_TAP_NAMES."""
+        """(rows, cols) of a tap without copying it (ws_debug_engine_tap with a NULL destination).  Names: TAP_NAMES /
+        TAP_NAMES_F16 (ECAPA-TDNN), RESNET_TAP_NAMES, SIMAM_TAP_NAMES, CAMPPLUS_TAP_NAMES, ERES2NET_TAP_NAMES."""
         rows, cols = ctypes.c_int32(0), ctypes.c_int32(0)
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().ws_debug_engine_tap(self._h, name.encode(), None, 0, ctypes.byref(rows),
@@ -314,6 +319,7 @@ class NativeSpeakerModel:
         """Diagnostic: a copy of the fp32 activation `name` (TAP_NAMES; ECAPA-TDNN) that the last chunk of the last
         forward left in the engine's workspace, as a (rows, cols) tensor on the GPU -- rows = B * T_slot for the
         frame-level tensors, B for se_s / stats / bias_img / pooled; channels contiguous (ws_debug_engine_tap).
+        TAP_NAMES_F16: the f16 back-end's binary16 tensors of the same forward, converted exactly to fp32.
         ResNet (RESNET_TAP_NAMES) and SimAM-ResNet (SIMAM_TAP_NAMES): stem / block / mid / sc / next_y1 of the last
         EXECUTED block as (B * H * W, C) in [b][f][t][c] order -- the models rotate four buffers, so an earlier block is
         read with stopped_after(n) --, and pooled / emb_a (ResNet), hid / logits / pooled (SimAM) after a full forward.
