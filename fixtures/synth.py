@@ -30,6 +30,22 @@ def synth_wav(utt_idx: int, num_samples: int = 32000) -> np.ndarray:
     return np.clip(np.rint(x), -32768, 32767).astype(np.int16)
 
 
+def synth_speaker_wav(spk_idx: int, num_samples: int, offset: int = 0) -> np.ndarray:
+    """PCM16 samples [offset, offset + num_samples) of synthetic "speaker" spk_idx: a fixed random spectrum (eight
+    tones between 150 Hz and 6 kHz whose frequencies and amplitudes depend on spk_idx alone) under a slow envelope,
+    plus a little noise.  Two windows of one speaker share a spectrum; two speakers do not -- what a diarization
+    test needs from its audio."""
+    rng = np.random.Generator(np.random.PCG64(77000 + int(spk_idx)))
+    freqs = rng.uniform(150.0, 6000.0, 8)
+    amps = rng.uniform(1000.0, 4000.0, 8)
+    phases = rng.uniform(0.0, 2 * np.pi, 8)
+    t = (offset + np.arange(num_samples, dtype=np.float64)) / SAMPLE_RATE
+    x = (amps[:, None] * np.sin(2 * np.pi * freqs[:, None] * t[None, :] + phases[:, None])).sum(0)
+    x *= 0.7 + 0.3 * np.sin(2 * np.pi * 0.9 * t)
+    noise = np.random.Generator(np.random.PCG64(88000 + 131 * int(spk_idx) + int(offset))).standard_normal(num_samples)
+    return np.clip(np.rint(x + 300.0 * noise), -32768, 32767).astype(np.int16)
+
+
 def synth_wav_batch(first_idx: int, batch: int, num_samples: int = 32000) -> np.ndarray:
     return np.stack([synth_wav(first_idx + i, num_samples) for i in range(batch)])
 

@@ -66,9 +66,10 @@ typedef void* ws_stream;                /* hipStream_t */
  * caller that relied on their refusing that family sees other results; 109: ws_debug_aff_fuse added, ws_engine_create
  * knows the ERes2Net34 names, ws_debug_engine_tap / ws_debug_engine_stop_after serve them; 110:
  * ws_debug_engine_stop_after serves ECAPA-TDNN (1 .. 3) and ws_debug_engine_tap reads its binary16 tensors -- a caller
- * that relied on the refusals sees other results).
+ * that relied on the refusals sees other results; 111: the ws_spectral_* entries, ws_debug_spectral_dense and
+ * ws_debug_spectral_mask added).
  * ws_version() returns the library's value: compare it with the header's before calling anything else. */
-#define WS_VERSION 110
+#define WS_VERSION 111
 WS_API int ws_version(void);
 WS_API const char* ws_last_error(void);
 /* Number of fbank frames for num_samples at snip_edges=True (25 ms / 10 ms):
@@ -474,6 +475,60 @@ WS_API int ws_cohort_stats(const float* unit, int n, const float* unit_cohort, i
 WS_API int ws_asnorm_pairs(const float* score, const int32_t* idx_e, const int32_t* idx_t,
                     const float* e_mean, const float* e_sd, const float* t_mean, const float* t_sd,
                     int64_t num_trials, float* out, ws_stream stream);
+
+/* ------------------------------------------------------------------------ spectral clustering
+ * The n-sized half of the reference's diarization clusterer, wespeaker/diar/spectral_clusterer.py:33-87
+ * (cluster()): affinity, pruning, Laplacian, and the products an iterative eigen-solver needs.  The b x b
+ * algebra of the solver and the k-means (:65-69) stay with the caller in float64 (wespeaker_amd/diar.py).
+ * 3 <= n <= 8192 everywhere (spectral_clusterer.py:72-73 answers n <= 2 without a graph; above 8192
+ * WS_ERR_CAPACITY: the transient n x n fp32 affinity is 256 MB there).  Panels X, Z, Y, LX are DEVICE
+ * float64 (n, b) row-major with 1 <= b <= 64. */
+/* spectral_clusterer.py:40-44: how many entries of a row of n survive prune(M, p) -- n - max(n - 10, 2)
+ * below 1000 rows, n - int((1 - p) * n) from 1000 on -- clamped to 0 .. n.  Pure function. */
+WS_API int ws_spectral_keep(int n, double p);
+/* Bytes of DEVICE scratch that ws_spectral_graph / ws_spectral_gram need for n rows of dim floats
+ * (0 for an n or dim they refuse). */
+WS_API int64_t ws_spectral_scratch(int n, int dim);
+/* Bytes of DEVICE scratch that ws_spectral_gram alone needs for n rows (its partial sums; at most 4 MiB): a
+ * caller that has released the graph's scratch -- it holds the n x n affinity -- keeps only this much for the
+ * solve (spectral_clusterer.py:59).  0 for an n it refuses. */
+WS_API int64_t ws_spectral_gram_scratch(int n);
+/* spectral_clusterer.py:35-56 up to the Laplacian's parts.  emb DEVICE float32 (n, dim) dense, rows are
+ * L2-normalised here (:36, no mean subtraction); the cosine matrix runs on the exact-fp32 MFMA GEMM of
+ * ws_cos_matrix (:37; 0.5 * (1 + cos) is monotone and is not materialised); each row keeps its `keep`
+ * largest entries (:46-50, keep = ws_spectral_keep(n, p)) -- EXACTLY keep of them: among values equal to
+ * the keep-th largest the higher column index stays, which is what the stable `np.argsort(row)[n:]` of :47-48
+ * keeps; P holds 1 there, M = (P + P^T) / 2 (:51), its diagonal is zeroed (:54).
+ * Out, all DEVICE: CSR of M -- rowptr int32[n + 1] (rowptr[n] = number of non-zeros), colidx int32[cap]
+ * ascending inside a row, vals float64[cap] (0.5 or 1) -- and deg float64[n] = row sums of M (:55), so that
+ * L = diag(deg) - M (:56).  cap >= min(n * (n - 1), 2 * n * keep) always suffices; nothing is written at
+ * or past cap, and a caller that passed less must compare rowptr[n] with it. */
+WS_API int ws_spectral_graph(const float* emb, int n, int dim, int keep, void* scratch, int64_t scratch_bytes,
+                      int32_t* rowptr, int32_t* colidx, double* vals, int64_t cap, double* deg,
+                      ws_stream stream);
+/* Y = alpha * (L X) + beta * X + gamma * Z with L X = deg (.) X - M X from the CSR (the Laplacian of
+ * spectral_clusterer.py:53-56 is never formed): one step of a three-term (Chebyshev) recurrence in one
+ * launch; beta = gamma = 0 gives the plain product.  Z may be NULL when gamma == 0; Y may be Z, not X.  The
+ * sum over a row's neighbours runs in CSR order: results are reproducible. */
+WS_API int ws_spectral_apply(const int32_t* rowptr, const int32_t* colidx, const double* vals, const double* deg,
+                      int n, int b, double alpha, double beta, double gamma, const double* X, const double* Z,
+                      double* Y, ws_stream stream);
+/* G = X^T X and H = X^T LX (DEVICE float64 (b, b) each) in one call: the reduced pair whose eigen-problem
+ * replaces scipy.linalg.eigh of the n x n Laplacian (spectral_clusterer.py:59).  The reduction order
+ * depends on (n, b) only -- no floating-point atomics -- so two calls give the same bits. */
+WS_API int ws_spectral_gram(const double* X, const double* LX, int n, int b, double* G, double* H, void* scratch,
+                     int64_t scratch_bytes, ws_stream stream);
+/* out = X W + gamma * Z, W DEVICE float64 (b, b) row-major: the basis update X <- X W of a Rayleigh-Ritz
+ * step (the eigenvectors of spectral_clusterer.py:59 are X W at convergence), and with W = -diag(theta),
+ * Z = LX, the residual panel L V - V theta.  out may be X (in place) or Z; Z may be NULL when gamma == 0. */
+WS_API int ws_spectral_rotate(const double* X, const double* W, double gamma, const double* Z, double* out, int n,
+                       int b, ws_stream stream);
+/* Debug / tests: the Laplacian of spectral_clusterer.py:53-56 densified, L DEVICE float64 (n, n). */
+WS_API int ws_debug_spectral_dense(const int32_t* rowptr, const int32_t* colidx, const double* vals,
+                            const double* deg, int n, double* L, ws_stream stream);
+/* Debug / tests: the pruning mask (spectral_clusterer.py:46-50, before symmetrisation) that the last
+ * ws_spectral_graph(n, dim) left in `scratch`; mask_out DEVICE uint32 (n, ceil(n / 32)), bit j of row i. */
+WS_API int ws_debug_spectral_mask(const void* scratch, int n, int dim, uint32_t* mask_out, ws_stream stream);
 
 #ifdef __cplusplus
 }

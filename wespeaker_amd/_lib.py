@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("WS_LIB_PATH") or os.path.join(_HERE, "lib", "libwespe
 
 _lib = None
 
-ABI_VERSION = 110      # = WS_VERSION of include/wespeaker_amd.h
+ABI_VERSION = 111      # = WS_VERSION of include/wespeaker_amd.h
 
 # name -> (restype, argtypes); also used by the ABI test to check every header symbol is exported
 SIGNATURES = {
@@ -95,6 +95,18 @@ SIGNATURES = {
                                 c_void_p, c_void_p, c_void_p]),
     "ws_asnorm_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_int64, c_void_p, c_void_p]),
+    "ws_spectral_keep": (c_int, [c_int, c_double]),
+    "ws_spectral_scratch": (c_int64, [c_int, c_int]),
+    "ws_spectral_gram_scratch": (c_int64, [c_int]),
+    "ws_spectral_graph": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                  c_int64, c_void_p, c_void_p]),
+    "ws_spectral_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_double,
+                                  c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ws_spectral_gram": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64,
+                                 c_void_p]),
+    "ws_spectral_rotate": (c_int, [c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "ws_debug_spectral_dense": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "ws_debug_spectral_mask": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
 }
 
 

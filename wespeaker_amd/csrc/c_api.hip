@@ -1108,4 +1108,169 @@ int ws_asnorm_pairs(const float* score, const int32_t* idx_e, const int32_t* idx
   return WS_OK;
 }
 
+// ------------------------------------------------------------------------ spectral clustering
+namespace {
+// The scratch of ws_spectral_graph, carved at 256-byte boundaries: unit table, fp32 affinity, mask, its
+// transpose, per-row counts.  ws_spectral_gram uses the front of the same buffer for its partials.
+int64_t spectral_gram_bytes(int n) { return (int64_t)spectral_gram_parts(n) * 2 * 4096 * 8; }
+struct SpectralLayout {
+  int64_t unit, aff, mask, maskT, count, total;
+};
+SpectralLayout spectral_layout(int n, int dim) {
+  auto up = [](int64_t v) { return (v + 255) & ~(int64_t)255; };
+  const int64_t n4 = (n + 3) & ~3, ld = (dim + 31) & ~31, words = (n + 31) / 32;
+  SpectralLayout l;
+  l.unit = 0;
+  l.aff = up(l.unit + n4 * ld * 4);
+  l.mask = up(l.aff + (int64_t)n * n4 * 4);
+  l.maskT = up(l.mask + (int64_t)n * words * 4);
+  l.count = up(l.maskT + (int64_t)n * words * 4);
+  l.total = up(l.count + (int64_t)n * 4);
+  const int64_t gram = spectral_gram_bytes(n);
+  if (l.total < gram) l.total = gram;
+  return l;
+}
+int spectral_check_n(const char* who, int n) {
+  if (n < 3) {
+    set_error("%s: invalid argument (n = %d: fewer than 3 rows have no graph, spectral_clusterer.py:72-73)", who, n);
+    return WS_ERR_INVALID_ARG;
+  }
+  if (n > SPECTRAL_MAX_N) {
+    set_error("%s: n = %d exceeds the limit of %d sub-segments (the transient n x n fp32 affinity is 256 MB there)",
+              who, n, SPECTRAL_MAX_N);
+    return WS_ERR_CAPACITY;
+  }
+  return WS_OK;
+}
+int spectral_check_b(const char* who, int b) {
+  if (b < 1 || b > SPECTRAL_MAX_B) {
+    set_error("%s: invalid argument (b = %d, a panel has 1 .. %d columns)", who, b, SPECTRAL_MAX_B);
+    return WS_ERR_INVALID_ARG;
+  }
+  return WS_OK;
+}
+}  // namespace
+
+int ws_spectral_keep(int n, double p) {
+  if (n <= 0) return 0;
+  // spectral_clusterer.py:40-44: the `n` lowest entries of a row are zeroed, the other m - n set to 1
+  const int low = n < 1000 ? (n - 10 > 2 ? n - 10 : 2) : (int)((1.0 - p) * n);
+  const int keep = n - low;
+  return keep < 0 ? 0 : (keep > n ? n : keep);
+}
+
+int64_t ws_spectral_scratch(int n, int dim) {
+  if (n < 3 || n > SPECTRAL_MAX_N || dim <= 0) return 0;
+  return spectral_layout(n, dim).total;
+}
+
+int64_t ws_spectral_gram_scratch(int n) {
+  if (n < 3 || n > SPECTRAL_MAX_N) return 0;
+  return spectral_gram_bytes(n);
+}
+
+int ws_spectral_graph(const float* emb, int n, int dim, int keep, void* scratch, int64_t scratch_bytes,
+                      int32_t* rowptr, int32_t* colidx, double* vals, int64_t cap, double* deg,
+                      ws_stream stream) {
+  if (!emb || !scratch || !rowptr || !colidx || !vals || !deg || dim <= 0 || keep < 0 || keep > n || cap < 0) {
+    set_error("ws_spectral_graph: invalid argument");
+    return WS_ERR_INVALID_ARG;
+  }
+  int r = spectral_check_n("ws_spectral_graph", n);
+  if (r) return r;
+  const SpectralLayout l = spectral_layout(n, dim);
+  if (scratch_bytes < l.total) {
+    set_error("ws_spectral_graph: scratch of %lld bytes is too small (ws_spectral_scratch(%d, %d) = %lld)",
+              (long long)scratch_bytes, n, dim, (long long)l.total);
+    return WS_ERR_CAPACITY;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  char* base = (char*)scratch;
+  float* unit = (float*)(base + l.unit);
+  float* aff = (float*)(base + l.aff);
+  uint32_t* mask = (uint32_t*)(base + l.mask);
+  uint32_t* maskT = (uint32_t*)(base + l.maskT);
+  int32_t* count = (int32_t*)(base + l.count);
+  const int n4 = ws_cos_table_rows(n);
+  // spectral_clusterer.py:35-37: rows / |row|, then the dot products (0.5 * (1 + .) keeps the order)
+  WS_HIP_CHECK(launch_cos_prepare(emb, nullptr, n, dim, unit, nullptr, st));
+  r = cos_gemm(unit, n, unit, n, ws_cos_table_ld(dim), aff, n4, st);
+  if (r) return r;
+  WS_HIP_CHECK(launch_spectral_mask(aff, n4, n, keep, mask, maskT, st));
+  WS_HIP_CHECK(launch_spectral_csr(mask, maskT, n, count, rowptr, cap, colidx, vals, deg, st));
+  return WS_OK;
+}
+
+int ws_debug_spectral_mask(const void* scratch, int n, int dim, uint32_t* mask_out, ws_stream stream) {
+  if (!scratch || !mask_out || dim <= 0) {
+    set_error("ws_debug_spectral_mask: invalid argument");
+    return WS_ERR_INVALID_ARG;
+  }
+  int r = spectral_check_n("ws_debug_spectral_mask", n);
+  if (r) return r;
+  const SpectralLayout l = spectral_layout(n, dim);
+  WS_HIP_CHECK(hipMemcpyAsync(mask_out, (const char*)scratch + l.mask, (size_t)n * ((n + 31) / 32) * 4,
+                              hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return WS_OK;
+}
+
+int ws_debug_spectral_dense(const int32_t* rowptr, const int32_t* colidx, const double* vals, const double* deg,
+                            int n, double* L, ws_stream stream) {
+  if (!rowptr || !colidx || !vals || !deg || !L) {
+    set_error("ws_debug_spectral_dense: invalid argument");
+    return WS_ERR_INVALID_ARG;
+  }
+  int r = spectral_check_n("ws_debug_spectral_dense", n);
+  if (r) return r;
+  WS_HIP_CHECK(launch_spectral_dense(rowptr, colidx, vals, deg, n, L, (hipStream_t)stream));
+  return WS_OK;
+}
+
+int ws_spectral_apply(const int32_t* rowptr, const int32_t* colidx, const double* vals, const double* deg, int n,
+                      int b, double alpha, double beta, double gamma, const double* X, const double* Z, double* Y,
+                      ws_stream stream) {
+  if (!rowptr || !colidx || !vals || !deg || !X || !Y || (gamma != 0.0 && !Z) || X == Y) {
+    set_error("ws_spectral_apply: invalid argument (NULL pointer, or Y aliases X)");
+    return WS_ERR_INVALID_ARG;
+  }
+  int r = spectral_check_n("ws_spectral_apply", n);
+  if (!r) r = spectral_check_b("ws_spectral_apply", b);
+  if (r) return r;
+  WS_HIP_CHECK(launch_spectral_apply(rowptr, colidx, vals, deg, n, b, alpha, beta, gamma, X, Z, Y,
+                                     (hipStream_t)stream));
+  return WS_OK;
+}
+
+int ws_spectral_gram(const double* X, const double* LX, int n, int b, double* G, double* H, void* scratch,
+                     int64_t scratch_bytes, ws_stream stream) {
+  if (!X || !LX || !G || !H || !scratch) {
+    set_error("ws_spectral_gram: invalid argument");
+    return WS_ERR_INVALID_ARG;
+  }
+  int r = spectral_check_n("ws_spectral_gram", n);
+  if (!r) r = spectral_check_b("ws_spectral_gram", b);
+  if (r) return r;
+  const int64_t need = spectral_gram_bytes(n);
+  if (scratch_bytes < need) {
+    set_error("ws_spectral_gram: scratch of %lld bytes is too small (need %lld)", (long long)scratch_bytes,
+              (long long)need);
+    return WS_ERR_CAPACITY;
+  }
+  WS_HIP_CHECK(launch_spectral_gram(X, LX, n, b, G, H, (double*)scratch, (hipStream_t)stream));
+  return WS_OK;
+}
+
+int ws_spectral_rotate(const double* X, const double* W, double gamma, const double* Z, double* out, int n, int b,
+                       ws_stream stream) {
+  if (!X || !W || !out || (gamma != 0.0 && !Z)) {
+    set_error("ws_spectral_rotate: invalid argument");
+    return WS_ERR_INVALID_ARG;
+  }
+  int r = spectral_check_n("ws_spectral_rotate", n);
+  if (!r) r = spectral_check_b("ws_spectral_rotate", b);
+  if (r) return r;
+  WS_HIP_CHECK(launch_spectral_rotate(X, W, gamma, Z, out, n, b, (hipStream_t)stream));
+  return WS_OK;
+}
+
 }  // extern "C"

@@ -448,4 +448,30 @@ hipError_t launch_asnorm_pairs(const float* score, const int32_t* idx_e, const i
                                const float* e_mean, const float* e_sd, const float* t_mean,
                                const float* t_sd, long long num, float* out, hipStream_t stream);
 
+// -------- spectral clustering (spectral.hip; diar/spectral_clusterer.py:33-63)
+// n <= SPECTRAL_MAX_N sub-segments (the mask kernel keeps one row's words in a 256-entry LDS table and the
+// transient affinity is n x n fp32: 256 MB at the limit); panels are n x b double, b <= SPECTRAL_MAX_B (one
+// wavefront lane per column).
+#define SPECTRAL_MAX_N 8192
+#define SPECTRAL_MAX_B 64
+// S (n, ld) fp32 affinity -> mask, maskT: (n, ceil(n/32)) words, exactly `keep` bits per row of mask
+hipError_t launch_spectral_mask(const float* S, int ld, int n, int keep, uint32_t* mask,
+                                uint32_t* maskT, hipStream_t stream);
+// mask, maskT -> CSR of M = (P + P^T)/2 without its diagonal (rowptr[n] = nnz; nothing is written at or
+// past `cap` entries) and deg = row sums; count: int32[n] work space
+hipError_t launch_spectral_csr(const uint32_t* mask, const uint32_t* maskT, int n, int32_t* count,
+                               int32_t* rowptr, long long cap, int32_t* colidx, double* vals,
+                               double* deg, hipStream_t stream);
+hipError_t launch_spectral_dense(const int32_t* rowptr, const int32_t* colidx, const double* vals,
+                                 const double* deg, int n, double* L, hipStream_t stream);
+hipError_t launch_spectral_apply(const int32_t* rowptr, const int32_t* colidx, const double* vals,
+                                 const double* deg, int n, int b, double alpha, double beta,
+                                 double gamma, const double* X, const double* Z, double* Y,
+                                 hipStream_t stream);
+int spectral_gram_parts(int n);            // partials of 2 x 64 x 64 doubles that launch_spectral_gram writes
+hipError_t launch_spectral_gram(const double* X, const double* LX, int n, int b, double* G, double* H,
+                                double* part, hipStream_t stream);
+hipError_t launch_spectral_rotate(const double* X, const double* W, double gamma, const double* Z,
+                                  double* out, int n, int b, hipStream_t stream);
+
 }  // namespace wsamd

@@ -14,6 +14,7 @@
 // (exact, ties included), then one pass accumulates sum and sum of squares above the threshold in
 // float64.  All of it is HBM/L2-bound streaming over the score rows; the GEMM is MFMA-bound.
 #include "kernels.h"
+#include "radix_select.h"
 
 namespace wsamd {
 
@@ -101,23 +102,12 @@ hipError_t launch_cos_pairs(const float* ua, const float* ub, int ld, const int3
 }
 
 // ------------------------------------------------------------------------------- top-N statistics
-// Order-preserving map float -> uint32 (larger float <=> larger key; -0 < +0 is harmless here).
-__device__ __forceinline__ uint32_t f2key(float v) {
-  const uint32_t b = __float_as_uint(v);
-  return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float key2f(uint32_t k) {
-  const uint32_t b = k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu);
-  return __uint_as_float(b);
-}
-
 // One workgroup per score row.  top_n_eff = min(top_n, n_cols) >= 1.
 // mean = (1/N) sum of the N largest scores; sd = sqrt((1/N) sum (x - mean)^2)  (np.std, ddof = 0).
 __global__ __launch_bounds__(256) void topn_stats_kernel(
     const float* __restrict__ S, int ld, int n_cols, int top_n_eff, float* __restrict__ mean,
     float* __restrict__ sd) {
-  __shared__ unsigned hist[4][256];          // one histogram per wavefront: 4x fewer collisions
-  __shared__ unsigned s_prefix, s_remaining;
+  __shared__ RadixSelectShared sel;         // the select itself: radix_select.h
   __shared__ double red[2][4];
   const int tid = threadIdx.x, wave = tid >> 6;
   const float* row = S + (long long)blockIdx.x * ld;
@@ -127,60 +117,7 @@ __global__ __launch_bounds__(256) void topn_stats_kernel(
   uint32_t thr_key = 0;                      // keys > thr_key are strictly inside the top-N
   unsigned ties = 0;                         // how many copies of thr_key complete the top-N
   const bool select = top_n_eff < n_cols;
-  if (select) {
-    if (tid == 0) { s_prefix = 0; s_remaining = (unsigned)top_n_eff; }
-    for (int pass = 0; pass < 4; ++pass) {
-      const int shift = 24 - 8 * pass;
-      for (int i = tid; i < 4 * 256; i += 256) (&hist[0][0])[i] = 0;
-      __syncthreads();
-      const uint32_t prefix = s_prefix;
-      auto vote = [&](float v) {
-        const uint32_t k = f2key(v);
-        if (pass == 0 || (k >> (shift + 8)) == prefix) atomicAdd(&hist[wave][(k >> shift) & 255], 1u);
-      };
-      for (int i = tid; i < nvec; i += 256) {
-        const f32x4s v = row4[i];
-        vote(v[0]); vote(v[1]); vote(v[2]); vote(v[3]);
-      }
-      for (int i = nvec * 4 + tid; i < n_cols; i += 256) vote(row[i]);
-      __syncthreads();
-      // bins from the top: find the one where the running count reaches `remaining`
-      if (wave == 0) {
-        const int lane = tid;
-        // lane l owns bins 255-4l .. 252-4l (descending order)
-        unsigned c[4], tot = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int b = 255 - (4 * lane + q);
-          c[q] = hist[0][b] + hist[1][b] + hist[2][b] + hist[3][b];
-          tot += c[q];
-        }
-        unsigned incl = tot;                 // inclusive prefix sum over lanes
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const unsigned up = __shfl_up(incl, o, 64);
-          if (lane >= o) incl += up;
-        }
-        const unsigned rem = s_remaining;
-        unsigned before = incl - tot;        // scores in strictly higher bins
-        if (before < rem && incl >= rem) {   // exactly one lane
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            if (before < rem && before + c[q] >= rem) {
-              s_prefix = (prefix << 8) | (unsigned)(255 - (4 * lane + q));
-              s_remaining = rem - before;
-              before = rem;                  // stop
-            } else {
-              before += c[q];
-            }
-          }
-        }
-      }
-      __syncthreads();
-    }
-    thr_key = s_prefix;
-    ties = s_remaining;
-  }
+  if (select) radix_select_row(row, n_cols, top_n_eff, sel, &thr_key, &ties);
 
   double s1 = 0.0, s2 = 0.0;
   auto take = [&](float v) {

@@ -5,9 +5,9 @@
     Speaker.extract_embedding / _from_pcm / _list / _from_feats, setters, cosine helpers (:60-211)
 
 Same names, argument meaning, return types and error behaviour; the arithmetic (fbank, CMN, model
-forward) runs in the HIP library on an MI355X.  Out-of-scope methods (VAD, diarization, model-hub
-download -- SURVEY.md section 2 rows 1/17) raise NotImplementedError instead of silently doing
-something else.
+forward) runs in the HIP library on an MI355X.  Out-of-scope methods (VAD and the `diarize` that starts with
+it, model-hub download -- SURVEY.md section 2 rows 1/17) raise NotImplementedError instead of silently doing
+something else; `diarize_segments` runs `diarize` from given speech segments on (wespeaker_amd/diar.py).
 """
 import os
 
@@ -312,6 +312,47 @@ class Speaker:
 
     def diarize_list(self, scp_path: str):
         raise NotImplementedError("diarization is outside the MI355X hot path")
+
+    def diarize_segments(self, audio_path_or_pcm, segments, utt: str = "unk", sample_rate=None):
+        """Steps 2-5 of `Speaker.diarize` (cli/speaker.py:224-270) for speech segments the caller supplies --
+        oracle SAD, a SAD file, or any VAD -- as a list of {'start': s, 'end': s} in seconds, the shape
+        `get_speech_timestamps(..., return_seconds=True)` returns (step 1, the silero VAD, is not here: `diarize`
+        keeps raising).  Segments shorter than `diar_min_duration` are dropped (:230); each of the others goes
+        through `extract_subsegment_embeddings` (:231-251, one device call); the embeddings are clustered on the
+        GPU (`wespeaker_amd.diar.cluster`, :255); window names become times (:259-264) and `merge_segments`
+        joins them (:268).  Returns the reference's list of (utt, begin, end, label).
+        `audio_path_or_pcm`: a wav path, or a (C, N) / (N,) tensor of int16-scale samples with `sample_rate`."""
+        from . import diar
+        if self.model.frontend_type != "fbank":            # (cli/speaker.py:214-215; load_model_pt builds no other)
+            raise NotImplementedError("diarization needs the fbank frontend, got %r" % (self.model.frontend_type,))
+        if isinstance(audio_path_or_pcm, (str, os.PathLike)):
+            pcm, sample_rate = load_wav(os.fspath(audio_path_or_pcm), normalize=False)
+        else:
+            pcm = torch.as_tensor(audio_path_or_pcm)
+            if sample_rate is None:
+                raise ValueError("sample_rate is required with samples")
+        pcm = pcm[0] if pcm.dim() == 2 else pcm.reshape(-1)
+        subsegs, embeddings = [], []
+        for item in segments:
+            begin, end = item["start"], item["end"]
+            if end - begin >= self.diar_min_duration:
+                seg = pcm[int(begin * sample_rate):int(end * sample_rate)].to(torch.float)
+                names, emb = self.extract_subsegment_embeddings(seg, sample_rate, int(begin * 1000), int(end * 1000))
+                subsegs.extend(names)
+                embeddings.append(emb)
+        if not subsegs:
+            return []
+        labels = diar.cluster(np.concatenate(embeddings), device=self.device)
+        windows = []
+        for name, label in zip(subsegs, labels):
+            _, w_begin, w_end = diar.window_times(name, self.diar_frame_shift)
+            windows.append([w_begin, w_end, int(label)])
+        return diar.merge_segments({utt: windows})
+
+    def make_rttm(self, merged_segment_to_labels, outfile):
+        """cli/speaker.py:283-289."""
+        from . import diar
+        diar.make_rttm(merged_segment_to_labels, outfile)
 
 
 def load_model(model_name_or_path: str, **kw) -> Speaker:
