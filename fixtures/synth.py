@@ -8,7 +8,7 @@ are too large to commit, e.g. 6 M-parameter weight sets).
 
 State-dict key names/shapes are the reference's parameter names
 (wespeaker/models/ecapa_tdnn.py:160-206, pooling_layers.py:97-117,
-resnet.py:110-169, campplus.py:333-407, eres2net.py:243-335) because the weight ingestion path
+resnet.py:110-169, campplus.py:333-407, eres2net.py:243-335, gemini_dfresnet.py:51-103) because the weight ingestion path
 (`load_model` -> `avg_model.pt`) is keyed by them.
 """
 from collections import OrderedDict
@@ -279,6 +279,43 @@ def synth_eres2net_state_dict(name="ERes2Net34_Base", feat_dim=80, embed_dim=512
     return g.sd
 
 
+GEMINI_LAYOUTS = {      # reference gemini_dfresnet.py:145-178: blocks per stage; dims [32, 32, 64, 128, 256] for all four
+    "Gemini_DF_ResNet60": [3, 3, 9, 3], "Gemini_DF_ResNet114": [3, 3, 27, 3],
+    "Gemini_DF_ResNet183": [3, 8, 45, 3], "Gemini_DF_ResNet237": [3, 8, 63, 3],
+}
+GEMINI_DIMS = (32, 32, 64, 128, 256)
+
+
+def synth_gemini_state_dict(name="Gemini_DF_ResNet60", feat_dim=80, embed_dim=256, two_emb_layer=False, seed=42):
+    """Gemini_DF_ResNet60 / 114 / 183 / 237 (gemini_dfresnet.py:51-103), keys in the module's own order.  The block's
+    last 1x1 convolution is damped (gain 0.02, as the Bottleneck conv3 of the deep ResNets) so that the residual sum
+    stays O(1) through the 63 blocks of the deepest stage; the downsample layers (no activation behind them) keep the
+    scale of their input."""
+    depths = GEMINI_LAYOUTS[name]
+    d = GEMINI_DIMS
+    g = _Init(seed)
+    g.conv("downsample_layers.0.0", d[0], 1, 3, 3, bias=False)
+    g.bn("downsample_layers.0.1", d[0])
+    for i in range(4):
+        g.conv("downsample_layers.%d.0" % (i + 1), d[i + 1], d[i], 3, 3, bias=False, gain=1.0)
+        g.bn("downsample_layers.%d.1" % (i + 1), d[i + 1])
+    for s, nb in enumerate(depths):
+        dim = d[s + 1]
+        for b in range(nb):
+            p = "stages.%d.%d" % (s, b)
+            g.conv(p + ".conv1", 4 * dim, dim, 1, 1, bias=False)
+            g.bn(p + ".bn1", 4 * dim)
+            g.conv(p + ".conv2", 4 * dim, 1, 3, 3, bias=False)
+            g.bn(p + ".bn2", 4 * dim)
+            g.conv(p + ".conv3", dim, 4 * dim, 1, 1, bias=False, gain=0.02)
+            g.bn(p + ".bn3", dim)
+    g.linear("seg_1", embed_dim, (feat_dim // 16) * d[4] * 2)
+    if two_emb_layer:
+        g.bn("seg_bn_1", embed_dim, affine=False)
+        g.linear("seg_2", embed_dim, embed_dim)
+    return g.sd
+
+
 def synth_campplus_state_dict(feat_dim=80, embed_dim=512, seed=42):
     g = _Init(seed)
     g.conv("head.conv1", 32, 1, 3, 3, bias=False)
@@ -337,6 +374,9 @@ def synth_state_dict(model_name, feat_dim=80, embed_dim=None, seed=42, **kw):
     if model_name.startswith("ERes2Net"):
         kw.pop("pooling_func", None)
         return synth_eres2net_state_dict(model_name, feat_dim, embed_dim or 512, seed=seed, **kw)
+    if model_name.startswith("Gemini_DF_ResNet"):
+        kw.pop("pooling_func", None)
+        return synth_gemini_state_dict(model_name, feat_dim, embed_dim or 256, seed=seed, **kw)
     raise KeyError("no synthetic weights for model %r" % model_name)
 
 

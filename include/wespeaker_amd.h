@@ -67,9 +67,10 @@ typedef void* ws_stream;                /* hipStream_t */
  * knows the ERes2Net34 names, ws_debug_engine_tap / ws_debug_engine_stop_after serve them; 110:
  * ws_debug_engine_stop_after serves ECAPA-TDNN (1 .. 3) and ws_debug_engine_tap reads its binary16 tensors -- a caller
  * that relied on the refusals sees other results; 111: the ws_spectral_* entries, ws_debug_spectral_dense and
- * ws_debug_spectral_mask added).
+ * ws_debug_spectral_mask added; 112: ws_debug_dwconv3x3 added, ws_engine_create knows the Gemini_DF_ResNet names,
+ * ws_debug_engine_tap / ws_debug_engine_stop_after serve them).
  * ws_version() returns the library's value: compare it with the header's before calling anything else. */
-#define WS_VERSION 111
+#define WS_VERSION 112
 WS_API int ws_version(void);
 WS_API const char* ws_last_error(void);
 /* Number of fbank frames for num_samples at snip_edges=True (25 ms / 10 ms):
@@ -293,6 +294,18 @@ WS_API int ws_debug_fbank_mode(int mode);
 WS_API int ws_debug_aff_fuse(const float* x, int ldx, int x_off, const float* y, int ldy, int y_off, float* out, int ldo,
                              int o_off, const float* w1, const float* b1, const float* w2, const float* b2, int rows,
                              int channels, const int32_t* row_len, int image_pixels, int image_width, ws_stream stream);
+/* Gemini DF-ResNet's depthwise 3x3 convolution (wespeaker/models/gemini_dfresnet.py:35-44: conv2 + bn2 + relu) as the
+ * engine runs it, on caller-supplied DEVICE buffers (tests/test_gpu_dwconv.py): over channels-last maps
+ * x[((b * height + f) * width + t)][channels]
+ *   out[b,f,t,c] = relu(sum_{df,dt in -1..1} x[b,f+df,t+dt,c] * w[c][3 (df+1) + (dt+1)] + bias[c])
+ * with zero padding on both axes and stride 1; w float32[channels][9] and bias [channels] carry the eval BatchNorm.
+ * channels: a multiple of 4; batch, height, width >= 1; fewer than 2^31 elements; pointers 16-byte aligned; out shares
+ * no element with x.  row_len (DEVICE int32[batch], or NULL): input pixels with t >= row_len[b] count as padding
+ * whatever they hold, output pixels there are stored as exact zeros, so a row of a ragged batch equals its batch-of-one
+ * result bit for bit.  WS_ERR_INVALID_ARG with the reason in ws_last_error for anything outside that contract; nothing
+ * is launched then. */
+WS_API int ws_debug_dwconv3x3(const float* x, float* out, const float* w, const float* bias, int batch, int height,
+                              int width, int channels, const int32_t* row_len, ws_stream stream);
 /* Read-only tap on the activations a forward leaves in the engine's workspace (no reference counterpart; the per-layer
  * parity tests of tests/test_gpu_layers.py).  A stream-ordered device-to-device copy of the named fp32 tensor as the
  * LAST chunk of the LAST forward on this engine left it (a batch beyond max_batch runs in chunks: the tap holds the
@@ -325,6 +338,9 @@ WS_API int ws_debug_aff_fuse(const float* x, int ldx, int x_off, const float* y,
  * ERes2Net names (tests/test_gpu_eres2net.py): stem (stopped at 0); of the last executed block: block, mid (conv1's
  * output, width * scale channels), cat (the concat conv3 reads), sc; after a full forward fuse12 / fuse123 / fuse1234
  * (the global fusions, rows = B * H * W of their level), pooled, and emb_a for two-embedding models.
+ * Gemini DF-ResNet names (tests/test_gpu_gemini.py): stem (stopped at 0); of the last executed stop point: ds (a
+ * downsample layer's output, no activation) or -- a block -- exp (conv1's output, 4 dim channels), dw (the depthwise
+ * kernel's output, 4 dim) and block (dim); pooled, and emb_a for two-embedding models, after a full forward.
  * CAM++ names (tests/test_gpu_campplus_layers.py).  The FCM head rotates three buffers and the trunk ping-pongs two, so
  * a stop point (ws_debug_engine_stop_after, stages 0 .. 9) selects what is read:
  *   stem     the stem's output, [b][f][t][32] as rows = B * F * T      -- only when stopped at 0
@@ -352,7 +368,7 @@ WS_API int ws_debug_aff_fuse(const float* x, int ldx, int x_off, const float* y,
  * the last chunk. */
 WS_API int ws_debug_engine_tap(ws_engine* eng, const char* name, float* dst, int64_t cap_floats, int32_t* rows,
                                int32_t* cols, ws_stream stream);
-/* Debug stop point (ResNet, SimAM-ResNet, ERes2Net, CAMPPlus, ECAPA-TDNN; no reference counterpart): every later forward on this
+/* Debug stop point (ResNet, SimAM-ResNet, ERes2Net, Gemini DF-ResNet, CAMPPlus, ECAPA-TDNN; no reference counterpart): every later forward on this
  * engine returns after the stem (n_blocks = 0) or after the last launch of the n-th residual block (a fused
  * conv3 + next-conv1 launch belongs to block n), so that ws_debug_engine_tap can read what those launches left.
  * Pooling and the head do not run; the embedding output is zero-filled on the stream.  -1 (the default) = the full
@@ -360,6 +376,8 @@ WS_API int ws_debug_engine_tap(ws_engine* eng, const char* name, float* dst, int
  * integer, tested once per block).  CAM++ counts stages instead of residual blocks: 0 = the stem, 1 .. 4 = the FCM
  * residual blocks, 5 = head.conv2, 6 = the TDNN layer, 7 / 8 / 9 = dense block 1 / 2 / 3 AND its transit.  ECAPA-TDNN
  * takes 1, 2 or 3: return after that SE-Res2 block (its SE scale + residual launch), layer 1 has no stop of its own.
+ * Gemini DF-ResNet counts its downsample layers too: 0 = the stem, then in forward order downsample layer 1, the blocks
+ * of stage 1, downsample layer 2, ... (4 + the number of blocks stop points).
  * WS_ERR_INVALID_ARG: n_blocks < -1 or beyond the model's block / stage count (ECAPA-TDNN: 0 as well); an engine that
  * is not finalized. */
 WS_API int ws_debug_engine_stop_after(ws_engine* eng, int n_blocks);

@@ -8,6 +8,7 @@ import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from wespeaker_amd import Frontend, NativeSpeakerModel
+from wespeaker_amd._lib import NativeError
 from fixtures import synth
 from bench import device_wavs
 
@@ -21,6 +22,10 @@ CASES = [  # (model, embed_dim, batch, chunk)
     ("ERes2Net34_Base", 512, 256, 256),            # the hub's eres2net asset (embed 512: the recipes' value)
     ("ERes2Net34_Large", 512, 128, 128),
     ("ERes2Net34_aug", 512, 64, 64),
+    ("Gemini_DF_ResNet60", 256, 256, 256),         # the four depths at 256 x 2 s (no f16 back-end: recorded as refused)
+    ("Gemini_DF_ResNet114", 256, 256, 256),        # the hub's Gemini_DFResnet114_LM
+    ("Gemini_DF_ResNet183", 256, 256, 256),
+    ("Gemini_DF_ResNet237", 256, 256, 256),
 ]
 
 def main():
@@ -44,7 +49,11 @@ def main():
         rec = {"model": name, "batch": batch, "engine_chunk": chunk, "frames": T,
                "gflop_per_utt": model.flops(1, T) / 1e9}
         for prec in ("fp32", "f16x3", "f16"):
-            model.set_precision(prec)
+            try:
+                model.set_precision(prec)
+            except NativeError as e:                # a family without that back-end says so by name
+                rec[prec] = {"refused": str(e)}
+                continue
             for _ in range(2):
                 model.extract(fe, wav)
             torch.cuda.synchronize()

@@ -264,6 +264,7 @@ int ws_engine_create(const char* model_name, int feat_dim, int embed_dim, int de
   if (!m) m = make_campplus(model_name, feat_dim, embed_dim);
   if (!m) m = make_samresnet(model_name, feat_dim, embed_dim);
   if (!m) m = make_eres2net(model_name, feat_dim, embed_dim);
+  if (!m) m = make_gemini(model_name, feat_dim, embed_dim);
   if (!m) {
     set_error("ws_engine_create: unknown model '%s'", model_name);
     return WS_ERR_UNKNOWN_MODEL;
@@ -735,6 +736,21 @@ int ws_debug_aff_fuse(const float* x, int ldx, int x_off, const float* y, int ld
     return WS_ERR_INVALID_ARG;
   }
   WS_HIP_CHECK(launch_aff_fuse(p, (hipStream_t)stream));
+  return WS_OK;
+}
+
+int ws_debug_dwconv3x3(const float* x, float* out, const float* w, const float* bias, int batch, int height, int width,
+                       int channels, const int32_t* row_len, ws_stream stream) {
+  DwConv3x3Params p;
+  std::memset(&p, 0, sizeof(p));
+  p.x = x; p.out = out; p.w = w; p.bias = bias;
+  p.B = batch; p.F = height; p.T = width; p.C = channels;
+  p.row_len = row_len;
+  if (const char* why = dwconv3x3_refusal(p)) {        // nothing is launched
+    set_error("ws_debug_dwconv3x3: %s (batch %d, height %d, width %d, channels %d)", why, batch, height, width, channels);
+    return WS_ERR_INVALID_ARG;
+  }
+  WS_HIP_CHECK(launch_dwconv3x3(p, (hipStream_t)stream));
   return WS_OK;
 }
 

@@ -209,7 +209,7 @@ struct Model {
   virtual int tap(const char* name, float* dst, int64_t cap_floats, int32_t* rows, int32_t* cols, hipStream_t stream) {
     (void)dst; (void)cap_floats; (void)rows; (void)cols; (void)stream;
     set_error("ws_debug_engine_tap: this model family has no activation taps (tensor '%s'; ECAPA-TDNN, ResNet, "
-              "SimAM-ResNet, ERes2Net and CAM++ have them)", name);
+              "SimAM-ResNet, ERes2Net, Gemini DF-ResNet and CAM++ have them)", name);
     return WS_ERR_INVALID_ARG;
   }
   // ws_debug_engine_stop_after: the 2-D families (ResNet, SimAM-ResNet) return from forward_chunk after the stem
@@ -232,6 +232,7 @@ Model* make_resnet(const std::string& model_name, int feat_dim, int embed_dim);
 Model* make_campplus(const std::string& model_name, int feat_dim, int embed_dim);
 Model* make_samresnet(const std::string& model_name, int feat_dim, int embed_dim);
 Model* make_eres2net(const std::string& model_name, int feat_dim, int embed_dim);
+Model* make_gemini(const std::string& model_name, int feat_dim, int embed_dim);
 
 }  // namespace wsamd
 

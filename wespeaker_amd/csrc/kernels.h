@@ -299,6 +299,22 @@ struct AffFuseParams {
 bool aff_fuse_supported(const AffFuseParams& p);
 const char* aff_fuse_refusal(const AffFuseParams& p);      // what aff_fuse_supported objects to (null: nothing)
 hipError_t launch_aff_fuse(const AffFuseParams& p, hipStream_t stream);
+// ---- Gemini DF-ResNet (dwconv3x3.hip)
+// Depthwise 3x3 convolution (padding 1, stride 1) + bias + ReLU over channels-last rows x[((b*F + f)*T + t)][C], fp32 VALU:
+//   out[b,f,t,c] = relu(sum_{df,dt in -1..1} x[b,f+df,t+dt,c] * w[c][3 (df+1) + (dt+1)] + bias[c])
+// w: [C][9], bias: [C] (an eval BatchNorm after the convolution is folded into both on the host).  C % 4 == 0; F, T >= 1;
+// fewer than 2^31 elements; 16-byte aligned pointers; out shares no element with x.  row_len (optional, as
+// ConvGemmParams::row_len): [B] valid widths -- input pixels with t >= row_len[b] count as padding whatever they hold,
+// output pixels there are stored as exact zeros.
+struct DwConv3x3Params {
+  const float* x; float* out;
+  const float* w; const float* bias;
+  int B, F, T, C;
+  const int* row_len;
+};
+bool dwconv3x3_supported(const DwConv3x3Params& p);
+const char* dwconv3x3_refusal(const DwConv3x3Params& p);   // what dwconv3x3_supported objects to (null: nothing)
+hipError_t launch_dwconv3x3(const DwConv3x3Params& p, hipStream_t stream);
 // CAM++ context (campplus.py:108-135): ctx = mean_T(h) + segmean_100(h); m = sigmoid(W2 relu(W1 ctx + b1) + b2)
 // h: [B*T][C] (C = 128); mask out: [B][segs][Cout]
 hipError_t launch_cam_context_from_colsum(const float* colsum, int B, int T, int C, const float* w1,

@@ -22,9 +22,10 @@ WINDOW_TYPES = {"hamming": 0, "povey": 1}
 SUPPORTED_MODELS = ("ECAPA_TDNN_c512", "ECAPA_TDNN_GLOB_c512", "ECAPA_TDNN_c1024",
                     "ECAPA_TDNN_GLOB_c1024", "ResNet18", "ResNet34", "ResNet50", "ResNet101",
                     "ResNet152", "ResNet221", "ResNet293", "CAMPPlus", "SimAM_ResNet34_ASP", "SimAM_ResNet100_ASP",
-                    "ERes2Net34_Base", "ERes2Net34_Large", "ERes2Net34_aug")
+                    "ERes2Net34_Base", "ERes2Net34_Large", "ERes2Net34_aug", "Gemini_DF_ResNet60", "Gemini_DF_ResNet114",
+                    "Gemini_DF_ResNet183", "Gemini_DF_ResNet237")
 
-DEFAULT_EMBED_DIM = {"ECAPA": 192, "ResNe": 256, "CAMPP": 512, "SimAM": 256, "ERes2": 512}
+DEFAULT_EMBED_DIM = {"ECAPA": 192, "ResNe": 256, "CAMPP": 512, "SimAM": 256, "ERes2": 512, "Gemin": 256}
 
 
 def simam_model_args(state_dict, feat_dim, model_args):
@@ -286,12 +287,17 @@ class NativeSpeakerModel:
     # the last executed block (stop_after 1..16); fuse12 / fuse123 / fuse1234 (the global fusions, (B*H*W, C) of their
     # level), pooled and -- two_emb_layer -- emb_a after a full forward
     ERES2NET_TAP_NAMES = ("stem", "block", "mid", "cat", "sc", "fuse12", "fuse123", "fuse1234", "pooled", "emb_a")
+    # Gemini_DF_ResNet*: stop_after counts the stem (0), then in forward order every downsample layer and every block;
+    # stem (stopped at 0); ds (the last executed stop point is a downsample layer) or exp / dw / block (it is a block:
+    # conv1's output and the depthwise kernel's, 4 dim channels, and the block's output); pooled / emb_a after a full forward
+    GEMINI_TAP_NAMES = ("stem", "ds", "exp", "dw", "block", "pooled", "emb_a")
 
     def stop_after(self, n_blocks):
-        """Diagnostic (ResNet / SimAM-ResNet / ERes2Net / CAMPPlus / ECAPA-TDNN; ws_debug_engine_stop_after): every later
-        forward returns after the stem (0) or after the n-th residual block (CAMPPlus: after stage n, see
-        CAMPPLUS_TAP_NAMES; ECAPA-TDNN: after SE-Res2 block 1, 2 or 3), its embeddings all zero, so that tap() reads that
-        block's tensors.
+        """Diagnostic (ResNet / SimAM-ResNet / ERes2Net / Gemini DF-ResNet / CAMPPlus / ECAPA-TDNN;
+        ws_debug_engine_stop_after): every later forward returns after the stem (0) or after the n-th residual block
+        (CAMPPlus: after stage n, see CAMPPLUS_TAP_NAMES; ECAPA-TDNN: after SE-Res2 block 1, 2 or 3; Gemini DF-ResNet: its
+        downsample layers count as stop points too, see GEMINI_TAP_NAMES), its embeddings all zero, so that tap() reads
+        that block's tensors.
         -1 restores the full forward.  Prefer `with model.stopped_after(n): ...`, which always restores it."""
         _lib.check(_lib.lib().ws_debug_engine_stop_after(self._h, int(n_blocks)), "ws_debug_engine_stop_after")
         return self
@@ -307,7 +313,8 @@ class NativeSpeakerModel:
 
     def tap_shape(self, name):
         """(rows, cols) of a tap without copying it (ws_debug_engine_tap with a NULL destination).  Names: TAP_NAMES /
-        TAP_NAMES_F16 (ECAPA-TDNN), RESNET_TAP_NAMES, SIMAM_TAP_NAMES, CAMPPLUS_TAP_NAMES, ERES2NET_TAP_NAMES."""
+        TAP_NAMES_F16 (ECAPA-TDNN), RESNET_TAP_NAMES, SIMAM_TAP_NAMES, CAMPPLUS_TAP_NAMES, ERES2NET_TAP_NAMES,
+        GEMINI_TAP_NAMES."""
         rows, cols = ctypes.c_int32(0), ctypes.c_int32(0)
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().ws_debug_engine_tap(self._h, name.encode(), None, 0, ctypes.byref(rows),
@@ -395,12 +402,13 @@ class NativeSpeakerModel:
         """Return convention of the reference modules (callers use `outputs[-1] if tuple`):
         ECAPA -> (out4, embed) (ecapa_tdnn.py:227-234), ResNet -> (tensor(0.0), embed_a) or
         (embed_a, embed_b) (resnet.py:192-204), CAM++ -> tensor (campplus.py:409-413), SimAM_ResNet*_ASP -> tensor
-        (samresnet.py:142-149), ERes2Net34_* -> tensor (eres2net.py:380-391).  The leading element is not materialised on this path (None for ECAPA / two-layer
-        ResNet)."""
+        (samresnet.py:142-149), ERes2Net34_* -> tensor (eres2net.py:380-391), Gemini_DF_ResNet* -> (tensor(0.0), embed_a)
+        or (embed_a, embed_b) (gemini_dfresnet.py:129-141).  The leading element is not materialised on this path (None for ECAPA / two-layer
+        ResNet and Gemini DF-ResNet)."""
         emb = self.embed(feats)
         if self.model_name.startswith(("CAMPPlus", "SimAM_ResNet", "ERes2Net")):
             return emb
-        if self.model_name.startswith("ResNet"):
+        if self.model_name.startswith(("ResNet", "Gemini_DF_ResNet")):
             return torch.tensor(0.0), emb
         return None, emb
 

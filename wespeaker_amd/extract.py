@@ -756,7 +756,7 @@ def build_gpu_extractor(configs, model_path, device=None, max_batch=256, max_fra
     fc = check_frontend_config(configs)
     margs = dict(configs.get("model_args") or {})
     pooling = margs.pop("pooling_func", None)
-    if configs["model"].startswith("ERes2Net") and pooling not in (None, "TSTP"):      # eres2net.py:326: any pooling layer;
+    if configs["model"].startswith(("ERes2Net", "Gemini_DF_ResNet")) and pooling not in (None, "TSTP"):      # eres2net.py:326: any pooling layer;
         raise NotImplementedError("%s with pooling_func=%r (only TSTP)" % (configs["model"], pooling))   # the engine has TSTP
     feat_dim = int(margs.pop("feat_dim", fc["num_mel_bins"]))
     embed_dim = margs.pop("embed_dim", None)

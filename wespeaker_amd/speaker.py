@@ -47,7 +47,7 @@ def load_model_pt(model_name_or_path: str, device=None, max_batch=64, max_frames
     pooling = model_args.pop("pooling_func", None)
     if config["model"].startswith("ECAPA") and pooling not in (None, "ASTP"):
         raise NotImplementedError("ECAPA-TDNN with pooling_func=%r (only ASTP)" % pooling)
-    if config["model"].startswith(("ResNet", "CAMPPlus", "ERes2Net")) and pooling not in (None, "TSTP"):
+    if config["model"].startswith(("ResNet", "CAMPPlus", "ERes2Net", "Gemini_DF_ResNet")) and pooling not in (None, "TSTP"):
         raise NotImplementedError("%s with pooling_func=%r (only TSTP)" % (config["model"], pooling))
     sd = _load_state_dict(os.path.join(model_dir, "avg_model.pt"))
     if model_args.pop("emb_bn", False) and "bn2.running_mean" not in sd:
