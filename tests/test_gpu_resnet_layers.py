@@ -608,3 +608,27 @@ def test_stop_and_tap_api_edges():
         with pytest.raises(NativeError, match="1, 2 or 3"):
             ecapa_engine("ECAPA_TDNN_c512").stop_after(n)
     ecapa_engine("ECAPA_TDNN_c512").stop_after(2).stop_after(-1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["ResNet34", S34, "ERes2Net34_Base"])
+def test_a_refused_reserve_leaves_the_engine_usable(name):
+    """ws_engine_reserve beyond 2^31 elements per activation map is refused before anything is re-laid-out: the
+    workspace, the activation buffers and their zero pads stay what they were, the next forward gives the same bits
+    and ws_engine_check_range still reads the pads."""
+    from wespeaker_amd._lib import NativeError
+    from wespeaker_amd.engine import NativeSpeakerModel
+    from test_gpu_eres2net_layers import _check_invariants    # (ws_engine_check_range in fp32 too: the zero pads)
+    model = NativeSpeakerModel(name, synth.synth_state_dict(name, 80, None, seed=42), feat_dim=80, max_batch=2,
+                               max_frames=64)
+    x = torch.from_numpy(np.ascontiguousarray(_fixture_feats()[:2, :57])).cuda()
+    before = model.embed(x).cpu().numpy()
+    with pytest.raises(NativeError, match="limit 2\\^31"):
+        model.reserve(1 << 20, 200)
+    assert (model.max_batch, model.max_frames) == (2, 64)
+    after = model.embed(x).cpu().numpy()
+    _check_invariants(model)
+    assert np.isfinite(before).all() and np.array_equal(before, after)
+    model.reserve(2, 64)                          # and an accepted one after it works as ever
+    assert np.array_equal(before, model.embed(x).cpu().numpy())
+    _check_invariants(model)

@@ -63,28 +63,14 @@ struct CamppModel : ModelBase {
   CamppModel(int fd, int ed) : ModelBase("CAMPPlus", fd, ed) {}
 
   bool wants(const std::string& key) const override {
-    if (key.size() > 20 && key.compare(key.size() - 19, 19, "num_batches_tracked") == 0)
-      return false;
-    return key.compare(0, 5, "head.") == 0 || key.compare(0, 8, "xvector.") == 0;
+    return wants_prefixes(key, {"head.", "xvector."});
   }
 
   int finalize(const SD& sd, int max_batch, int max_frames) override {
     int err = 0;
     if (feat_dim % 8) { set_error("CAMPPlus needs feat_dim %% 8 == 0"); return WS_ERR_INVALID_ARG; }
     fprime = feat_dim / 8;
-    {
-      const HostTensor* wt = get(sd, "head.conv1.weight", {32, 1, 3, 3}, &err);
-      if (!wt) return err;
-      std::vector<double> sc, sh;
-      if ((err = bn_affine(sd, "head.bn1", 32, &sc, &sh))) return err;
-      std::vector<float> wf(32 * 9), bf(32);
-      for (int c = 0; c < 32; ++c) {
-        for (int k = 0; k < 9; ++k) wf[c * 9 + k] = (float)(wt->data[c * 9 + k] * sc[c]);
-        bf[c] = (float)sh[c];
-      }
-      stem_w = arena.add(wf);
-      stem_b = arena.add(bf);
-    }
+    if ((err = pack_stem3x3(sd, "head.conv1", "head.bn1", 32, &stem_w, &stem_b))) return err;
     for (int i = 0; i < 4; ++i) {
       const std::string p = std::string("head.layer") + (i < 2 ? "1." : "2.") + std::to_string(i & 1);
       res[i].stride = (i & 1) ? 1 : 2;
@@ -157,24 +143,18 @@ struct CamppModel : ModelBase {
     last_chunk = LastChunk();                  // the taps address the old layout
     cam_taps = CamTaps();
     const size_t img = (size_t)maxB * feat_dim * maxT * 32;        // FCM full-resolution activation
-    // (32-bit element offsets in the binary16 convolution kernels: one engine chunk stays below 2^31 elements)
-    if (img >= (size_t)1 << 31) {
-      set_error("CAMPPlus: max_batch %d x max_frames %d puts %zu elements in one activation map (limit 2^31); "
-                "use a smaller engine chunk", max_batch, max_frames, img);
-      return WS_ERR_CAPACITY;
-    }
+    if ((err = refuse_map_too_large(img))) return err;
     const int Tp = (maxT - 1) / 2 + 1;
     const size_t Mp = (size_t)maxB * Tp;
     max_segs = (Tp + 99) / 100;
-    size_t total = 0;
-    auto take = [&](size_t n) { size_t o = total; total += (n + 63) & ~size_t(63); return o; };
-    size_t o_fa = take(img), o_fb = take(img / 2 + 64), o_fc = take(img / 2 + 64),
-           o_x = take(Mp * 1024), o_x2 = take(Mp * 1024), o_h = take(Mp * 128),
-           o_mask = take((size_t)maxB * max_segs * 32), o_pool = take((size_t)maxB * 1024),
-           o_colsum = take(((Mp + 63) / 64 + 2) * 2 * 128),
-           o_part = take((size_t)kSplitK * maxB * embed_dim),
-           o_feats = take((size_t)maxB * maxT * feat_dim);
-    if ((err = alloc_workspace(total))) return err;
+    Carve cv;
+    size_t o_fa = cv.take(img), o_fb = cv.take(img / 2 + 64), o_fc = cv.take(img / 2 + 64),
+           o_x = cv.take(Mp * 1024), o_x2 = cv.take(Mp * 1024), o_h = cv.take(Mp * 128),
+           o_mask = cv.take((size_t)maxB * max_segs * 32), o_pool = cv.take((size_t)maxB * 1024),
+           o_colsum = cv.take(((Mp + 63) / 64 + 2) * 2 * 128),
+           o_part = cv.take((size_t)kSplitK * maxB * embed_dim),
+           o_feats = cv.take((size_t)maxB * maxT * feat_dim);
+    if ((err = alloc_workspace(cv.total))) return err;
     float* base = ws.as<float>();
     fa = base + o_fa; fb = base + o_fb; fc = base + o_fc; xbuf = base + o_x; xbuf2 = base + o_x2;
     colsum = base + o_colsum;
@@ -403,10 +383,7 @@ struct CamppModel : ModelBase {
 
   // ws_debug_engine_tap: what the last chunk's last executed stages left in the workspace (see CamTaps)
   int tap(const char* tname, float* dst, int64_t cap_floats, int32_t* rows, int32_t* cols, hipStream_t st) override {
-    if (!last_chunk.B) {
-      set_error("ws_debug_engine_tap: no forward has run on this engine since it was finalized / re-sized");
-      return WS_ERR_INVALID_ARG;
-    }
+    if (int r = tap_guard()) return r;
     const CamTaps& t = cam_taps;
     const std::string n = tname;
     char why[200] = "";

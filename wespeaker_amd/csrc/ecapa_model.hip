@@ -37,13 +37,7 @@ struct EcapaModel : ModelBase {
   }
 
   bool wants(const std::string& key) const override {
-    static const char* prefixes[] = {"layer1.", "layer2.", "layer3.", "layer4.", "conv.",
-                                     "pool.", "bn.", "linear.", "bn2."};
-    if (key.size() > 20 && key.compare(key.size() - 19, 19, "num_batches_tracked") == 0)
-      return false;
-    for (auto p : prefixes)
-      if (key.compare(0, std::strlen(p), p) == 0) return true;
-    return false;
+    return wants_prefixes(key, {"layer1.", "layer2.", "layer3.", "layer4.", "conv.", "pool.", "bn.", "linear.", "bn2."});
   }
 
   int finalize(const SD& sd, int max_batch, int max_frames) override {
@@ -113,17 +107,16 @@ struct EcapaModel : ModelBase {
     maxB = max_batch; maxT = max_frames;
     last_chunk = LastChunk();                  // the taps address the old layout
     const size_t M = (size_t)maxB * maxT;
-    size_t total = 0;
-    auto take = [&](size_t n) { size_t o = total; total += (n + 63) & ~size_t(63); return o; };
-    size_t o_out1 = take(M * C), o_y1 = take(M * C), o_y2 = take(M * C), o_y3 = take(M * C),
-           o_cat = take(M * 3 * C), o_h = take(M * 1536), o_att = take(M * 128),
-           o_e = take(M * 1536), o_s = take((size_t)maxB * C), o_stats = take((size_t)maxB * 3072),
-           o_bias = take((size_t)maxB * 128), o_pool = take((size_t)maxB * 3072),
-           o_part = take((size_t)kSplitK * maxB * (embed_dim > 128 ? embed_dim : 128)),
-           o_h16 = take((M * (size_t)(1536 + 3 * C + C + 128 + C + C + 512) + 1) / 2),   // binary16 copies (f16 back-end)
-           o_colsum = take(((M + 63) / 64 + 2) * 2 * (C > 1536 ? C : 1536)),
-           o_colsumsq = take(((M + 63) / 64 + 2) * 2 * 1536), o_feats = take(M * feat_dim);
-    if ((err = alloc_workspace(total))) return err;
+    Carve cv;
+    size_t o_out1 = cv.take(M * C), o_y1 = cv.take(M * C), o_y2 = cv.take(M * C), o_y3 = cv.take(M * C),
+           o_cat = cv.take(M * 3 * C), o_h = cv.take(M * 1536), o_att = cv.take(M * 128),
+           o_e = cv.take(M * 1536), o_s = cv.take((size_t)maxB * C), o_stats = cv.take((size_t)maxB * 3072),
+           o_bias = cv.take((size_t)maxB * 128), o_pool = cv.take((size_t)maxB * 3072),
+           o_part = cv.take((size_t)kSplitK * maxB * (embed_dim > 128 ? embed_dim : 128)),
+           o_h16 = cv.take((M * (size_t)(1536 + 3 * C + C + 128 + C + C + 512) + 1) / 2),   // binary16 copies (f16 back-end)
+           o_colsum = cv.take(((M + 63) / 64 + 2) * 2 * (C > 1536 ? C : 1536)),
+           o_colsumsq = cv.take(((M + 63) / 64 + 2) * 2 * 1536), o_feats = cv.take(M * feat_dim);
+    if ((err = alloc_workspace(cv.total))) return err;
     float* base = ws.as<float>();
     out1 = base + o_out1; y1 = base + o_y1; y2 = base + o_y2; y3 = base + o_y3; cat = base + o_cat;
     h = base + o_h; att = base + o_att; e = base + o_e; se_s = base + o_s; stats = base + o_stats;
@@ -379,11 +372,8 @@ struct EcapaModel : ModelBase {
   // ws_debug_engine_tap: the tensors forward_chunk leaves behind (layout: reserve(); [rows][cols] contiguous).  The plain
   // names are the fp32 tensors; the *16 names are the binary16 tensors of the f16 back-end, widened exactly.
   int tap(const char* name, float* dst, int64_t cap_floats, int32_t* rows, int32_t* cols, hipStream_t st) override {
+    if (int r = tap_guard()) return r;
     const LastChunk& lc = last_chunk;
-    if (lc.B <= 0) {
-      set_error("ws_debug_engine_tap: no forward has run on this engine since it was finalized / re-sized");
-      return WS_ERR_INVALID_ARG;
-    }
     const int M = lc.B * lc.T;
     const char* half = "the f16 back-end with T >= 64 keeps it in binary16 only: read the name with the suffix 16";
     const char* noglob = "only the GLOB models compute the context statistics";

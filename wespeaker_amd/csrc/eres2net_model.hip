@@ -9,13 +9,13 @@
 //   wespeaker/models/eres2net.py:243-391   ERes2Net (4 stages, 3 stride-2 downsample convs, 3 global AFFs, TSTP, seg_1 [seg_2])
 //   wespeaker/models/eres2net.py:394-430   the three constructors
 //
-// Layout and BN folding as in resnet_model.hip (channels-last [b][f][t][c] fp32, conv -> BN folded on the host).  A
+// Layout, BN folding, the zero-padded activation buffers, the seg_1 / seg_2 head and the shared taps: cnn2d_base.h.  A
 // block keeps conv1's output (`mid`, width * scale channels) and the concat that conv3 reads (`cat`) as two buffers of
 // that row width: branch i reads the channel slice i of mid (ConvGemmParams::a_off) plus -- layers 1 - 2, i >= 1 --
 // slice i - 1 of cat through ConvGemmParams::A2, and writes slice i of cat (d_off); in layers 3 - 4 aff_fuse blends
 // slice i - 1 of cat with slice i of mid into a width-wide scratch that the branch convolution reads.  The global
 // fusions run as soon as their inputs exist (fuse12 right after layer 2, ...): same values, shorter lifetimes.
-#include "model_common.h"
+#include "cnn2d_base.h"
 
 #include <algorithm>
 
@@ -41,49 +41,30 @@ struct ERes2Block {
   int stride = 1, in_planes = 0, planes = 0, width = 0, stage = 0;
 };
 
-bool starts_with(const std::string& s, const char* p) { return s.compare(0, std::strlen(p), p) == 0; }
-
-struct ERes2NetModel : ModelBase {
+struct ERes2NetModel : Cnn2dBase {
   ERes2Layout lay;
-  static constexpr int kSplitK = 16;
-  static constexpr int kBufs = 14;
-  size_t stem_w = 0, stem_b = 0;
   std::vector<ERes2Block> blocks;
-  ConvW down[3], seg1, seg2;
+  ConvW down[3];
   AffW gfuse[3];
-  size_t seg_bn_scale = 0, seg_bn_shift = 0;
-  bool two_emb = false;
-  int stats_dim = 0;
-  // activation buffers, each followed by 512 zero floats: the stage outputs L[0..3], the block ping-pong P[0..1], conv1's
-  // output, the concat, the shortcut's output, the AFF scratch, the downsample output, the three global fusions
+  // the fourteen activation buffers (Cnn2dBase::buf, carved in this order): the stage outputs L[0..3], the block ping-pong
+  // P[0..1], conv1's output, the concat, the shortcut's output, the AFF scratch, the downsample output, the three global
+  // fusions
   enum { B_L0 = 0, B_P0 = 4, B_MID = 6, B_CAT = 7, B_SC = 8, B_SP = 9, B_DS = 10, B_F0 = 11 };
-  float* buf[kBufs] = {};
-  size_t cap[kBufs] = {};
-  float *pooled = nullptr, *partial = nullptr, *emb_a = nullptr;
-  // taps of the last chunk beyond ModelBase::BlockTaps
+  // taps of the last chunk beyond Cnn2dBase::BlockTaps
   const float* tap_cat = nullptr;
   int tap_cat_c = 0;
   int fuse_rows[3] = {0, 0, 0};
 
-  ERes2NetModel(const ERes2Layout& l, int fd, int ed) : ModelBase(l.name, fd, ed), lay(l) {}
+  ERes2NetModel(const ERes2Layout& l, int fd, int ed) : Cnn2dBase(l.name, fd, ed), lay(l) {}
 
   bool wants(const std::string& key) const override {
-    if (key.size() > 20 && key.compare(key.size() - 19, 19, "num_batches_tracked") == 0) return false;
-    static const char* prefixes[] = {"conv1.", "bn1.", "layer1.", "layer2.", "layer3.", "layer4.", "layer1_downsample.",
-                                     "layer2_downsample.", "layer3_downsample.", "fuse_mode12.", "fuse_mode123.",
-                                     "fuse_mode1234.", "seg_1.", "seg_bn_1.", "seg_2."};
-    for (auto p : prefixes)
-      if (starts_with(key, p)) return true;
-    return false;
+    return wants_prefixes(key, {"conv1.", "bn1.", "layer1.", "layer2.", "layer3.", "layer4.", "layer1_downsample.",
+                                "layer2_downsample.", "layer3_downsample.", "fuse_mode12.", "fuse_mode123.",
+                                "fuse_mode1234.", "seg_1.", "seg_bn_1.", "seg_2."});
   }
 
   int set_precision(int mode) override {
-    if (mode == 2) {
-      set_error("%s has no binary16-tensor back-end (precision mode 2): its AFF kernel is fp32; use mode 0 (fp32) or 1 "
-                "(f16x3)", name.c_str());
-      return WS_ERR_INVALID_ARG;
-    }
-    return ModelBase::set_precision(mode);
+    return mode == 2 ? no_f16io_backend("its AFF kernel is") : ModelBase::set_precision(mode);
   }
 
   // AFF(channels = C): Conv2d(2C -> C/4, 1x1, bias) + BN, SiLU, Conv2d(C/4 -> C, 1x1, bias) + BN   (eres2net.py:81-95)
@@ -119,19 +100,7 @@ struct ERes2NetModel : ModelBase {
                 "ERes2Net34_Large / ERes2Net34_aug 64)", name.c_str(), got, m);
       return WS_ERR_SHAPE;
     }
-    {   // stem: Conv2d(1, m, 3x3) + bn1 folded -> [C][9] + [C]
-      const HostTensor* wt = get(sd, "conv1.weight", {m, 1, 3, 3}, &err);
-      if (!wt) return err;
-      std::vector<double> sc, sh;
-      if ((err = bn_affine(sd, "bn1", m, &sc, &sh))) return err;
-      std::vector<float> wf(m * 9), bf(m);
-      for (int c = 0; c < m; ++c) {
-        for (int k = 0; k < 9; ++k) wf[c * 9 + k] = (float)(wt->data[c * 9 + k] * sc[c]);
-        bf[c] = (float)sh[c];
-      }
-      stem_w = arena.add(wf);
-      stem_b = arena.add(bf);
-    }
+    if ((err = pack_stem3x3(sd, "conv1", "bn1", m, &stem_w, &stem_b))) return err;      // Conv2d(1, m, 3x3) + bn1
     int in_planes = m;
     for (int s = 0; s < 4; ++s) {
       const int planes = m << s;
@@ -166,6 +135,7 @@ struct ERes2NetModel : ModelBase {
         blocks.push_back(blk);
       }
     }
+    n_stops = (int)blocks.size();
     static const char* fnames[3] = {"fuse_mode12", "fuse_mode123", "fuse_mode1234"};
     for (int k = 0; k < 3; ++k) {
       const int cin = m * E << k, cout = cin * 2;
@@ -174,29 +144,18 @@ struct ERes2NetModel : ModelBase {
       if ((err = pack_aff(sd, fnames[k], cout, &gfuse[k]))) return err;
     }
     stats_dim = (feat_dim / 8) * m * 8 * E;                      // eres2net.py:261,326-327
-    if ((err = pack_linear(sd, "seg_1", embed_dim, 2 * stats_dim, true, &seg1))) return err;
-    two_emb = sd.count("seg_2.weight") > 0;
-    if (two_emb) {
-      if ((err = add_bn_vectors(sd, "seg_bn_1", embed_dim, &seg_bn_scale, &seg_bn_shift, false))) return err;
-      if ((err = pack_linear(sd, "seg_2", embed_dim, embed_dim, true, &seg2))) return err;
-    }
+    if ((err = pack_seg_head(sd))) return err;
     if ((err = upload_weights())) return err;
     return reserve(max_batch, max_frames);
   }
 
-  static int level_len(int L, int level) {
-    for (int l = 0; l < level; ++l) L = (L - 1) / 2 + 1;
-    return L;
-  }
   int stage_c(int s) const { return (lay.m * lay.expansion) << s; }           // channels of a stage's output
   int stage_w(int s) const { return (lay.m << s) * lay.base_width / 64; }     // branch width of a stage
 
   int reserve(int max_batch, int max_frames) override {
     int err = 0;
-    maxB = max_batch; maxT = max_frames;
-    last_chunk = LastChunk();
-    block_taps = BlockTaps();
-    tap_cat = nullptr;
+    begin_reserve(max_batch, max_frames);
+    tap_cat = nullptr; tap_cat_c = 0;
     auto map = [&](int s, int c) { return (size_t)maxB * level_len(feat_dim, s) * level_len(maxT, s) * (size_t)c; };
     size_t big = 0, mid = 0, sp = 0;
     for (int s = 0; s < 4; ++s) {
@@ -206,66 +165,17 @@ struct ERes2NetModel : ModelBase {
       if (s >= 2) sp = std::max(sp, map(s, stage_w(s)));
     }
     big = std::max(big, map(0, lay.m));
-    if (big >= (size_t)1 << 31) {
-      set_error("%s: max_batch %d x max_frames %d puts %zu elements in one activation map (limit 2^31); "
-                "use a smaller engine chunk", name.c_str(), max_batch, max_frames, big);
-      return WS_ERR_CAPACITY;
-    }
-    if (maxB > 65535) {
-      set_error("%s: max_batch %d exceeds 65535 (one grid row per utterance)", name.c_str(), max_batch);
-      return WS_ERR_CAPACITY;
-    }
-    for (int s = 0; s < 4; ++s) cap[B_L0 + s] = map(s, stage_c(s));
-    cap[B_P0] = cap[B_P0 + 1] = big;
-    cap[B_MID] = cap[B_CAT] = mid;
-    cap[B_SC] = big;
-    cap[B_SP] = sp;
-    cap[B_DS] = map(1, stage_c(1));
-    for (int k = 0; k < 3; ++k) cap[B_F0 + k] = map(k + 1, stage_c(k + 1));
-    size_t total = 0;
-    auto take = [&](size_t n) { size_t o = total; total += (n + 63) & ~size_t(63); return o; };
-    size_t ob[kBufs];
-    // (+ 512 zero floats behind every activation buffer, never written: border taps of the 3x3 convolutions'
-    // persistent form -- ConvGemmParams::a_zero_off -- and the tripwire of check_invariants)
-    for (int i = 0; i < kBufs; ++i) ob[i] = take(cap[i] + 512);
-    const size_t o_pool = take((size_t)maxB * 2 * stats_dim), o_part = take((size_t)kSplitK * maxB * embed_dim),
-                 o_emba = take((size_t)maxB * embed_dim), o_feats = take((size_t)maxB * maxT * feat_dim);
-    if ((err = alloc_workspace(total))) return err;
-    float* base = ws.as<float>();
-    for (int i = 0; i < kBufs; ++i) {
-      buf[i] = base + ob[i];
-      if (hipMemset(buf[i] + cap[i], 0, 512 * sizeof(float)) != hipSuccess) {
-        set_error("zero pad of activation buffer %d", i);
-        return WS_ERR_HIP;
-      }
-    }
-    pooled = base + o_pool; partial = base + o_part; emb_a = base + o_emba; feats_ws = base + o_feats;
-    reserved = true;
-    if (hipDeviceSynchronize() != hipSuccess) return WS_ERR_HIP;
-    return 0;
+    if ((err = refuse_map_too_large(big)) || (err = refuse_batch_too_large())) return err;
+    Carve cv = begin_carve();
+    for (int s = 0; s < 4; ++s) buf.carve(cv, map(s, stage_c(s)));                 // B_L0 + s
+    // B_P0, B_P0 + 1, B_MID, B_CAT, B_SC, B_SP, B_DS
+    for (size_t c : {big, big, mid, mid, big, sp, map(1, stage_c(1))}) buf.carve(cv, c);
+    for (int k = 0; k < 3; ++k) buf.carve(cv, map(k + 1, stage_c(k + 1)));         // B_F0 + k
+    return alloc_with_seg_head(cv);
   }
-  bool reserved = false;
 
   // TSTP's unbiased variance needs two frames at the last stage: 9 -> 5 -> 3 -> 2
   int min_frames() const override { return 9; }
-
-  int check_invariants() override {
-    if (!reserved) return 0;
-    std::vector<float> pad(512);
-    for (int i = 0; i < kBufs; ++i) {
-      if (hipMemcpy(pad.data(), buf[i] + cap[i], 512 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-        set_error("%s: reading the zero pad of activation buffer %d failed", name.c_str(), i);
-        return WS_ERR_HIP;
-      }
-      for (int k = 0; k < 512; ++k)
-        if (pad[k] != 0.f) {
-          set_error("%s: the zero pad behind activation buffer %d was overwritten (float %d = %g): a kernel stored "
-                    "past its tensor; convolution borders of later forwards are wrong", name.c_str(), i, k, pad[k]);
-          return WS_ERR_STATE;
-        }
-    }
-    return 0;
-  }
 
   hipError_t aff(const AffW& w, const float* x, int ldx, int x_off, const float* y, int ldy, int y_off, float* out,
                  int ldo, int o_off, int M, int HW, int W, const int* row_len, hipStream_t st) {
@@ -283,27 +193,22 @@ struct ERes2NetModel : ModelBase {
   }
 
   int forward_chunk(const float* feats, int B, int T, float* emb, hipStream_t st) override {
-    if (gemm_precision == 2) {               // (set_precision refuses it; never read fp32 buffers as halves)
-      set_error("%s has no binary16-tensor back-end (precision mode 2)", name.c_str());
-      return WS_ERR_STATE;
-    }
-    last_chunk.B = 0;
-    tap_cat = nullptr;
+    if (gemm_precision == 2) return no_f16io_backend();      // (set_precision refuses it)
+    BlockTaps& tp = begin_chunk();             // host-side notes for ws_debug_engine_tap, readable when the chunk ends
+    tap_cat = nullptr; tap_cat_c = 0;
     const int m = lay.m, SC = lay.scale;
     int H = feat_dim, W = T, lvl = 0;
     float* x = buf[B_P0];
     WS_LAUNCH(other(4.0 * B * H * (double)W * (m + 1), st, [&] {
       return launch_stem_conv3x3_any(feats, B, T, feat_dim, arena.at(stem_w), arena.at(stem_b), m, x, st, cur_lens[0]);
     }));
-    BlockTaps tp;                              // host-side notes for ws_debug_engine_tap, stored when the chunk ends
     tp.n_exec = 0; tp.stem = x; tp.stem_rows = B * H * W; tp.stem_c = m;
-    if (stop_after == 0) return end_chunk(tp, false, B, T, emb, st);
+    if (stop_after == 0) return end_chunk(false, B, T, emb, st);
     auto conv = [&](const ConvW& cw, const float* in, int lda, int a_off, float* out, int ldd, int d_off, int Hin_,
                     int Win_, int s_, int pad, int act, int out_lvl) {
       ConvGemmParams p = conv2d(cw, in, lda, a_off, out, ldd, d_off, B, Hin_, Win_, s_, s_, 1, 1, pad, pad, act);
       p.row_len = cur_lens[out_lvl];                       // stride level of this launch's OUTPUT width
-      for (int i = 0; i < kBufs; ++i)                     // the zero pad behind the input's buffer
-        if (in == buf[i] && cw.Cin <= 512) p.a_zero_off = (long long)cap[i] * (long long)sizeof(float);
+      p.a_zero_off = buf.zero_off_for(in, cw.Cin);         // the zero pad behind the input's buffer
       return p;
     };
     float* const mid = buf[B_MID];
@@ -351,7 +256,7 @@ struct ERes2NetModel : ModelBase {
         tp.mid = mid; tp.mid_c = ws_;
         tp.sc = blk.has_sc ? scb : nullptr;
         tap_cat = cat; tap_cat_c = ws_;
-        if (stop) return end_chunk(tp, false, B, T, emb, st);
+        if (stop) return end_chunk(false, B, T, emb, st);
       }
       if (last_of_stage && blk.stage >= 1) {
         // bottom-up fusion (eres2net.py:361-368): fuse_k = AFF(out_k, downsample(previous)), previous = out1 / fuse12 / fuse123
@@ -363,42 +268,8 @@ struct ERes2NetModel : ModelBase {
         fuse_rows[k] = M;
       }
     }
-    const int Cl = stage_c(3);
-    const float* last = buf[B_F0 + 2];
-    WS_LAUNCH(other(8.0 * B * H * (double)W * Cl, st, [&] {
-      return launch_tstp(last, Cl, B, H, W, Cl, nullptr, nullptr, pooled, st, cur_lens[lvl]);
-    }));
-    if (!two_emb) {
-      WS_LAUNCH(gemm_splitk(conv1d(seg1, pooled, 2 * stats_dim, 0, emb, embed_dim, 0, B, 1, 1, ACT_NONE),
-                            partial, kSplitK, st));
-    } else {            // embed_b = seg_2(seg_bn_1(relu(seg_1(stats))))   (eres2net.py:384-389)
-      ConvGemmParams a = conv1d(seg1, pooled, 2 * stats_dim, 0, emb_a, embed_dim, 0, B, 1, 1, ACT_RELU);
-      a.post_scale = arena.at(seg_bn_scale); a.post_shift = arena.at(seg_bn_shift);
-      WS_LAUNCH(gemm_splitk(a, partial, kSplitK, st));
-      WS_LAUNCH(gemm(conv1d(seg2, emb_a, embed_dim, 0, emb, embed_dim, 0, B, 1, 1, ACT_NONE), st));
-    }
-    tp.head_rows = B;
-    return end_chunk(tp, true, B, T, emb, st);
-  }
-
-  // the chunk is enqueued: remember what it left; a stopped one (ws_debug_engine_stop_after) returns zeros
-  int end_chunk(BlockTaps& tp, bool full, int B, int T, float* emb, hipStream_t st) {
-    tp.full = full;
-    if (!full)
-      if (int r = stop_chunk(emb, B, st)) return r;
-    block_taps = tp;
-    last_chunk.B = B; last_chunk.T = T; last_chunk.prec = gemm_precision;
-    return 0;
-  }
-
-  int set_stop_after(int n) override {
-    if (n < -1 || n > (int)blocks.size()) {
-      set_error("ws_debug_engine_stop_after: n_blocks = %d, %s has %d residual blocks (-1 = the full forward, 0 = after "
-                "the stem)", n, name.c_str(), (int)blocks.size());
-      return WS_ERR_INVALID_ARG;
-    }
-    stop_after = n;
-    return WS_OK;
+    // pooling and the head read the last global fusion   (eres2net.py:370-389)
+    return pool_and_head(buf[B_F0 + 2], stage_c(3), B, H, W, lvl, T, emb, st);
   }
 
   // ws_debug_engine_tap: 'stem' when stopped at 0; of the last executed block 'block' (its output), 'mid' (conv1's
@@ -406,28 +277,13 @@ struct ERes2NetModel : ModelBase {
   // forward 'fuse12' / 'fuse123' / 'fuse1234' (the global fusions, [b][f][t][c] rows), 'pooled' and -- two-embedding
   // models -- 'emb_a' (seg_1's output after its relu + seg_bn_1 epilogue, what seg_2 reads)
   int tap(const char* tname, float* dst, int64_t cap_floats, int32_t* rows, int32_t* cols, hipStream_t st) override {
-    if (!last_chunk.B) {
-      set_error("ws_debug_engine_tap: no forward has run on this engine since it was finalized / re-sized");
-      return WS_ERR_INVALID_ARG;
-    }
+    if (int r = tap_guard()) return r;
     const BlockTaps& t = block_taps;
     const std::string n = tname;
     char why[200];
-    if (n == "stem") {
-      std::snprintf(why, sizeof(why), "the last forward ran %d blocks over the stem's buffer: stop it at 0 "
-                    "(ws_debug_engine_stop_after)", t.n_exec);
-      return tap_copy(tname, t.n_exec == 0 ? t.stem : nullptr, why, t.stem_rows, t.stem_c, dst, cap_floats, rows, cols, st);
-    }
-    if (n == "block" || n == "mid" || n == "cat" || n == "sc") {
-      if (t.n_exec < 1)
-        return tap_copy(tname, nullptr, "the last forward was stopped after the stem: no block ran", 0, 0, dst,
-                        cap_floats, rows, cols, st);
-      std::snprintf(why, sizeof(why), "block %d has no shortcut convolution", t.n_exec);
-      if (n == "block") return tap_copy(tname, t.block, why, t.rows, t.block_c, dst, cap_floats, rows, cols, st);
-      if (n == "mid") return tap_copy(tname, t.mid, why, t.rows, t.mid_c, dst, cap_floats, rows, cols, st);
-      if (n == "cat") return tap_copy(tname, tap_cat, why, t.rows, tap_cat_c, dst, cap_floats, rows, cols, st);
-      return tap_copy(tname, t.sc, why, t.rows, t.block_c, dst, cap_floats, rows, cols, st);
-    }
+    if (n == "cat")                            // (null only when no block ran)
+      return tap_copy(tname, tap_cat, "the last forward was stopped after the stem: no block ran", t.rows, tap_cat_c, dst,
+                      cap_floats, rows, cols, st);
     std::snprintf(why, sizeof(why), "the last forward was stopped after block %d: the global fusions, pooling and the "
                   "head did not run", t.n_exec);
     for (int k = 0; k < 3; ++k) {
@@ -436,15 +292,8 @@ struct ERes2NetModel : ModelBase {
         return tap_copy(tname, t.full ? buf[B_F0 + k] : nullptr, why, fuse_rows[k], stage_c(k + 1), dst, cap_floats, rows,
                         cols, st);
     }
-    if (n == "pooled")
-      return tap_copy(tname, t.full ? pooled : nullptr, why, t.head_rows, 2 * stats_dim, dst, cap_floats, rows, cols, st);
-    if (n == "emb_a")
-      return tap_copy(tname, !two_emb ? nullptr : (t.full ? emb_a : nullptr),
-                      two_emb ? why : "the model has one embedding layer (no seg_2)", t.head_rows, embed_dim, dst,
-                      cap_floats, rows, cols, st);
-    set_error("ws_debug_engine_tap: unknown tensor '%s' (%s: stem, block, mid, cat, sc, fuse12, fuse123, fuse1234, "
-              "pooled, emb_a)", tname, name.c_str());
-    return WS_ERR_INVALID_ARG;
+    return tap_shared(tname, dst, cap_floats, rows, cols, st,
+                      {"stem, block, mid, cat, sc, fuse12, fuse123, fuse1234, pooled, emb_a", why});
   }
 
   double flops(int batch, int T) const override {
@@ -465,9 +314,7 @@ struct ERes2NetModel : ModelBase {
       const double px = (double)level_len(feat_dim, k + 1) * level_len(T, k + 1), cin = stage_c(k), cout = stage_c(k + 1);
       macs += px * 9 * cin * cout + px * aff_macs(cout);
     }
-    macs += 2.0 * stats_dim * embed_dim;
-    if (two_emb) macs += (double)embed_dim * embed_dim;
-    return 2.0 * macs * batch;
+    return 2.0 * (macs + seg_head_macs()) * batch;
   }
 };
 

@@ -53,6 +53,19 @@ struct ModelBase : Model {
   ModelBase(const std::string& n, int fd, int ed) : name(n), feat_dim(fd), embed_dim(ed) {
     zeros_off = arena.add(nullptr, 64);
   }
+  static bool starts_with(const std::string& s, const char* p) { return s.compare(0, std::strlen(p), p) == 0; }
+  // Model::wants of every family: the keys under its state_dict prefixes, without BatchNorm's step counters
+  static bool wants_prefixes(const std::string& key, std::initializer_list<const char*> prefixes) {
+    if (key.size() > 20 && key.compare(key.size() - 19, 19, "num_batches_tracked") == 0) return false;
+    for (const char* p : prefixes)
+      if (starts_with(key, p)) return true;
+    return false;
+  }
+  // workspace carving of reserve(): running float offsets, every slice rounded up to 64 floats
+  struct Carve {
+    size_t total = 0;
+    size_t take(size_t n) { size_t o = total; total += (n + 63) & ~size_t(63); return o; }
+  };
   int set_precision(int mode) override {
     if (mode < 0 || mode > 2) return WS_ERR_INVALID_ARG;
     gemm_precision = mode;
@@ -88,6 +101,24 @@ struct ModelBase : Model {
   size_t lens_cap = 0;
   hipEvent_t lens_copied = nullptr;
   bool ragged() const { return cur_lens[0] != nullptr; }
+  static int level_len(int L, int level) {
+    for (int l = 0; l < level; ++l) L = (L - 1) / 2 + 1;
+    return L;
+  }
+  // reserve(): the binary16 convolution kernels address a tensor with 32-bit element offsets, so one engine chunk keeps
+  // every activation map below 2^31 elements (larger batches are processed in chunks anyway) ...
+  int refuse_map_too_large(size_t elems) {
+    if (elems < (size_t)1 << 31) return 0;
+    set_error("%s: max_batch %d x max_frames %d puts %zu elements in one activation map (limit 2^31); "
+              "use a smaller engine chunk", name.c_str(), maxB, maxT, elems);
+    return WS_ERR_CAPACITY;
+  }
+  // ... and the kernels with one grid row per utterance take 65535 of them
+  int refuse_batch_too_large() {
+    if (maxB <= 65535) return 0;
+    set_error("%s: max_batch %d exceeds 65535 (one grid row per utterance)", name.c_str(), maxB);
+    return WS_ERR_CAPACITY;
+  }
 
   virtual int forward_chunk(const float* feats, int B, int T, float* emb, hipStream_t st) = 0;
   virtual int min_frames() const = 0;
@@ -106,20 +137,18 @@ struct ModelBase : Model {
   } last_chunk;
   // ---- debug stop point of the 2-D families and CAM++ (ws_debug_engine_stop_after): -1 = the full forward, 0 = return
   // after the stem, n = after the n-th residual block (CAM++: after stage n).  The families with a block loop override
-  // set_stop_after to validate n.
+  // set_stop_after to validate n (the 2-D ones through Cnn2dBase, cnn2d_base.h, which also keeps their taps).
   int stop_after = -1;
-  // what a stopped chunk's tensors are: one block's worth of pointers into the rotating buffers (host side only)
-  struct BlockTaps {
-    int n_exec = -1;             // blocks the last chunk executed (0: the stem alone; -1: nothing to read)
-    bool full = false;           // the chunk ran to its end: the pooling / head tensors exist
-    bool half = false;           // the maps exist as binary16 only (f16 back-end)
-    const float *stem = nullptr, *block = nullptr, *mid = nullptr, *sc = nullptr, *next_y1 = nullptr;
-    int stem_rows = 0, stem_c = 0, rows = 0, block_c = 0, mid_c = 0, next_c = 0, head_rows = 0;
-  } block_taps;
   // a stopped chunk's embedding rows: zeros, not whatever the caller's buffer held
   int stop_chunk(float* emb, int B, hipStream_t st) {
     WS_HIP_CHECK(hipMemsetAsync(emb, 0, (size_t)B * embed_dim * sizeof(float), st));
     return 0;
+  }
+  // every tap() starts here: nothing to read before a chunk has run to its end on the current workspace layout
+  int tap_guard() {
+    if (last_chunk.B > 0) return 0;
+    set_error("ws_debug_engine_tap: no forward has run on this engine since it was finalized / re-sized");
+    return WS_ERR_INVALID_ARG;
   }
   // one entry of a family's tap table: rows x cols fp32 at src (null: not produced in fp32), contiguous or -- src_ld > 0
   // -- with a row stride of src_ld floats (CAM++'s transit output lies in the next dense block's wider buffer)
@@ -187,15 +216,12 @@ struct ModelBase : Model {
       (void)hipEventSynchronize(lens_copied);          // the previous upload has left the staging buffer
     }
     for (int b = 0; b < batch; ++b) {
-      int L = lens_host[b];
+      const int L = lens_host[b];
       if (L < min_frames() || L > frames) {
         set_error("ragged batch: utterance %d has %d frames, valid range is [%d, %d]", b, L, min_frames(), frames);
         return nullptr;
       }
-      for (int l = 0; l < kLenLevels; ++l) {
-        lens_pinned[(size_t)l * batch + b] = L;
-        L = (L - 1) / 2 + 1;
-      }
+      for (int l = 0; l < kLenLevels; ++l) lens_pinned[(size_t)l * batch + b] = level_len(L, l);
     }
     if (hipMemcpyAsync(lens_dev.ptr, lens_pinned, (size_t)batch * kLenLevels * sizeof(int),
                        hipMemcpyHostToDevice, st) != hipSuccess ||
@@ -342,6 +368,24 @@ struct ModelBase : Model {
     std::vector<float> f(sc.begin(), sc.end()), g(sh.begin(), sh.end());
     *scale = arena.add(f);
     *shift = arena.add(g);
+    return 0;
+  }
+
+  // A (C, 1, 3, 3) convolution with the BatchNorm behind it folded in (float64) -> [C][9] weights + [C] bias: the
+  // single-channel stem of the 2-D families and CAM++, and Gemini's depthwise conv2 (groups = C)
+  int pack_stem3x3(const SD& sd, const std::string& conv, const std::string& bn, int C, size_t* w_off, size_t* b_off) {
+    int err = 0;
+    const HostTensor* wt = get(sd, conv + ".weight", {C, 1, 3, 3}, &err);
+    if (!wt) return err;
+    std::vector<double> sc, sh;
+    if ((err = bn_affine(sd, bn, C, &sc, &sh))) return err;
+    std::vector<float> wf((size_t)C * 9), bf(C);
+    for (int c = 0; c < C; ++c) {
+      for (int k = 0; k < 9; ++k) wf[(size_t)c * 9 + k] = (float)((double)wt->data[(size_t)c * 9 + k] * sc[c]);
+      bf[c] = (float)sh[c];
+    }
+    *w_off = arena.add(wf);
+    *b_off = arena.add(bf);
     return 0;
   }
 

@@ -7,11 +7,9 @@
 //   wespeaker/models/resnet.py:207-260  ctor names
 //   wespeaker/models/pooling_layers.py:78-85 TSTP
 //
-// Layout: the (B, T, F) feature tensor is the single-channel (F x T) image; every activation is
-// channels-last [b][f][t][c] fp32, so each Conv2d is one implicit GEMM with K = kh*kw*Cin contiguous.
-// conv -> BN has no non-linearity in between, so every BatchNorm2d is folded into its conv's
-// weights + bias on the host (float64); the residual add and ReLU live in the GEMM epilogue.
-#include "model_common.h"
+// Layout, BN folding, the zero-padded activation buffers, the seg_1 / seg_2 head and the shared taps: cnn2d_base.h.  The
+// residual add and ReLU live in the GEMM epilogue.
+#include "cnn2d_base.h"
 
 namespace wsamd {
 
@@ -31,32 +29,18 @@ struct Block {
   int stride = 1, in_planes = 0, planes = 0;
 };
 
-struct ResNetModel : ModelBase {
+struct ResNetModel : Cnn2dBase {
   Layout lay;
   int exp = 1;
-  size_t stem_w = 0, stem_b = 0;
-  std::vector<Block> blocks;
-  ConvW seg1, seg2;
-  bool two_emb = false;
-  size_t seg_bn_scale = 0, seg_bn_shift = 0;
-  float* buf[4] = {nullptr, nullptr, nullptr, nullptr};
-  size_t act_floats = 0;                     // floats per activation buffer (512 zero floats follow each)
-  float *pooled = nullptr, *partial = nullptr, *emb_a = nullptr;
-  int stats_dim = 0;
-  static constexpr int kSplitK = 16;
+  std::vector<Block> blocks;                 // (the four rotating activation buffers: Cnn2dBase::buf)
 
-  ResNetModel(const Layout& l, int fd, int ed) : ModelBase(l.name, fd, ed), lay(l) {
+  ResNetModel(const Layout& l, int fd, int ed) : Cnn2dBase(l.name, fd, ed), lay(l) {
     exp = l.bottleneck ? 4 : 1;
   }
 
   bool wants(const std::string& key) const override {
-    if (key.size() > 20 && key.compare(key.size() - 19, 19, "num_batches_tracked") == 0)
-      return false;
-    static const char* prefixes[] = {"conv1.", "bn1.", "layer1.", "layer2.", "layer3.", "layer4.",
-                                     "seg_1.", "seg_bn_1.", "seg_2."};
-    for (auto p : prefixes)
-      if (key.compare(0, std::strlen(p), p) == 0) return true;
-    return false;
+    return wants_prefixes(key, {"conv1.", "bn1.", "layer1.", "layer2.", "layer3.", "layer4.", "seg_1.", "seg_bn_1.",
+                                "seg_2."});
   }
 
   int finalize(const SD& sd, int max_batch, int max_frames) override {
@@ -66,19 +50,7 @@ struct ResNetModel : ModelBase {
       set_error("ResNet needs feat_dim %% 8 == 0, got %d", feat_dim);
       return WS_ERR_INVALID_ARG;
     }
-    {   // stem: Conv2d(1, 32, 3x3) + bn1 folded -> [C][9] + [C]
-      const HostTensor* wt = get(sd, "conv1.weight", {m, 1, 3, 3}, &err);
-      if (!wt) return err;
-      std::vector<double> sc, sh;
-      if ((err = bn_affine(sd, "bn1", m, &sc, &sh))) return err;
-      std::vector<float> wf(m * 9), bf(m);
-      for (int c = 0; c < m; ++c) {
-        for (int k = 0; k < 9; ++k) wf[c * 9 + k] = (float)(wt->data[c * 9 + k] * sc[c]);
-        bf[c] = (float)sh[c];
-      }
-      stem_w = arena.add(wf);
-      stem_b = arena.add(bf);
-    }
+    if ((err = pack_stem3x3(sd, "conv1", "bn1", m, &stem_w, &stem_b))) return err;      // Conv2d(1, 32, 3x3) + bn1
     int in_planes = m;
     for (int s = 0; s < 4; ++s) {
       const int planes = m << s;
@@ -105,80 +77,25 @@ struct ResNetModel : ModelBase {
         blocks.push_back(blk);
       }
     }
+    n_stops = (int)blocks.size();
     stats_dim = (feat_dim / 8) * m * 8 * exp;          // C_last * F_last   (resnet.py:123)
-    if ((err = pack_linear(sd, "seg_1", embed_dim, 2 * stats_dim, true, &seg1))) return err;
-    two_emb = sd.count("seg_2.weight") > 0;
-    if (two_emb) {
-      if ((err = add_bn_vectors(sd, "seg_bn_1", embed_dim, &seg_bn_scale, &seg_bn_shift, false))) return err;
-      seg1.scale = seg_bn_scale; seg1.shift = seg_bn_shift;     // relu -> BN(affine=False) epilogue
-      if ((err = pack_linear(sd, "seg_2", embed_dim, embed_dim, true, &seg2))) return err;
-    }
+    if ((err = pack_seg_head(sd))) return err;
     if ((err = upload_weights())) return err;
     return reserve(max_batch, max_frames);
   }
 
   int reserve(int max_batch, int max_frames) override {
-    int err = 0;
-    maxB = max_batch; maxT = max_frames;
-    last_chunk = LastChunk();                  // the taps address the old layout
-    block_taps = BlockTaps();
+    begin_reserve(max_batch, max_frames);
     // largest activation: stage-1 output (F x T x 32*exp); scratch planes are never larger
+    // (below 2^31 elements: ~4200 x 2 s utterances for BasicBlock nets, ~1060 for Bottleneck nets)
     const size_t act = (size_t)maxB * feat_dim * maxT * (size_t)(32 * exp);
-    // (the binary16 convolution kernels address a tensor with 32-bit element offsets: one engine chunk keeps
-    // every activation map below 2^31 elements -- ~4200 x 2 s utterances for BasicBlock nets, ~1060 for
-    // Bottleneck nets; larger batches are processed in chunks anyway)
-    if (act >= (size_t)1 << 31) {
-      set_error("%s: max_batch %d x max_frames %d puts %zu elements in one activation map (limit 2^31); "
-                "use a smaller engine chunk", name.c_str(), max_batch, max_frames, act);
-      return WS_ERR_CAPACITY;
-    }
-    size_t total = 0;
-    auto take = [&](size_t n) { size_t o = total; total += (n + 63) & ~size_t(63); return o; };
-    size_t ob[4];
-    // (+ 512 floats of zeros behind every activation buffer, never written: the border taps of the persistent
-    // kernel's CONV form read Cin <= 512 of them -- ConvGemmParams::a_zero_off)
-    for (int i = 0; i < 4; ++i) ob[i] = take(act + 512);
-    act_floats = act;
-    size_t o_pool = take((size_t)maxB * 2 * stats_dim),
-           o_part = take((size_t)kSplitK * maxB * embed_dim), o_emba = take((size_t)maxB * embed_dim),
-           o_feats = take((size_t)maxB * maxT * feat_dim);
-    if ((err = alloc_workspace(total))) return err;
-    float* base = ws.as<float>();
-    for (int i = 0; i < 4; ++i) {
-      buf[i] = base + ob[i];
-      if (hipMemset(buf[i] + act, 0, 512 * sizeof(float)) != hipSuccess) {
-        set_error("zero pad of activation buffer %d", i);
-        return WS_ERR_HIP;
-      }
-    }
-    pooled = base + o_pool; partial = base + o_part; emb_a = base + o_emba; feats_ws = base + o_feats;
-    // (hipMemset runs on the null stream, the forwards on the caller's: the pads are zero before reserve() returns)
-    if (hipDeviceSynchronize() != hipSuccess) return WS_ERR_HIP;
-    return 0;
+    if (int err = refuse_map_too_large(act)) return err;
+    Carve cv = begin_carve();
+    for (int i = 0; i < 4; ++i) buf.carve(cv, act);          // the block rotation
+    return alloc_with_seg_head(cv);
   }
 
   int min_frames() const override { return 2; }
-
-  //  The CONV form of the persistent GEMM reads border taps from the 512 zero floats behind each activation
-  // buffer.  Nothing may ever store there -- a whole-tile store without a row guard would, and every later image
-  // border would be silently wrong: ws_engine_check_range looks (8 KB device -> host, behind its synchronisation).
-  int check_invariants() override {
-    if (!act_floats) return 0;
-    std::vector<float> pad(512);
-    for (int i = 0; i < 4; ++i) {
-      if (hipMemcpy(pad.data(), buf[i] + act_floats, 512 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-        set_error("%s: reading the zero pad of activation buffer %d failed", name.c_str(), i);
-        return WS_ERR_HIP;
-      }
-      for (int k = 0; k < 512; ++k)
-        if (pad[k] != 0.f) {
-          set_error("%s: the zero pad behind activation buffer %d was overwritten (float %d = %g): a kernel stored "
-                    "past its tensor; convolution borders of later forwards are wrong", name.c_str(), i, k, pad[k]);
-          return WS_ERR_STATE;
-        }
-    }
-    return 0;
-  }
 
   int forward_chunk(const float* feats, int B, int T, float* emb, hipStream_t st) override {
     int H = feat_dim, W = T;
@@ -189,22 +106,20 @@ struct ResNetModel : ModelBase {
     // all convolutions then run on the LDS-DMA kernel (conv form), residuals are read as halfs
     const bool f16io = gemm_precision == 2;
     float* x = buf[0];
-    last_chunk.B = 0;                          // (taps: nothing to read until this chunk has been enqueued)
+    BlockTaps& tp = begin_chunk();             // host-side notes for ws_debug_engine_tap, readable when the chunk ends
     WS_LAUNCH(other(4.0 * B * H * (double)W * 33, st, [&] {
       return launch_stem_conv3x3(feats, B, T, feat_dim, arena.at(stem_w), arena.at(stem_b), 32, x, st,
                                  f16io ? reinterpret_cast<uint16_t*>(x) : nullptr, cur_lens[0]);
     }));
-    BlockTaps tp;                              // host-side notes for ws_debug_engine_tap, stored when the chunk ends
     tp.half = f16io;
-    tp.n_exec = 0; tp.stem = x; tp.stem_rows = B * H * W; tp.stem_c = 32; tp.head_rows = B;
-    if (stop_after == 0) return end_chunk(tp, false, B, T, emb, st);
+    tp.n_exec = 0; tp.stem = x; tp.stem_rows = B * H * W; tp.stem_c = 32;
+    if (stop_after == 0) return end_chunk(false, B, T, emb, st);
     // in -> out convolution with the optional residual, in the tensor format of the active back-end
     auto conv = [&](const ConvW& cw, const float* in, int Cin_, float* out, int Cout_, int Hin_, int Win_,
                     int s_, int pad, int act, const float* res, int ldr, int out_lvl) {
       ConvGemmParams p = conv2d(cw, in, Cin_, 0, out, Cout_, 0, B, Hin_, Win_, s_, s_, 1, 1, pad, pad, act);
       p.row_len = cur_lens[out_lvl];                       // stride level of this launch's OUTPUT width
-      for (int i = 0; i < 4; ++i)                          // the zero pad behind the input's buffer
-        if (in == buf[i] && Cin_ <= 512) p.a_zero_off = (long long)act_floats * (long long)sizeof(float);
+      p.a_zero_off = buf.zero_off_for(in, Cin_);           // the zero pad behind the input's buffer
       if (f16io) {
         p.A16 = reinterpret_cast<const uint16_t*>(in); p.lda16 = Cin_;
         p.D = nullptr; p.D16 = reinterpret_cast<uint16_t*>(out); p.ldd16 = Cout_;
@@ -289,94 +204,29 @@ struct ResNetModel : ModelBase {
         tp.sc = blk.has_sc ? t2 : nullptr;
         tp.next_y1 = have_y1 ? buf[y1_idx] : nullptr;
         tp.next_c = have_y1 ? blocks[bi + 1].planes : 0;
-        if (stop) return end_chunk(tp, false, B, T, emb, st);
+        if (stop) return end_chunk(false, B, T, emb, st);
       }
     }
     const int Cl = 256 * exp;           // channels of the last stage
-    WS_LAUNCH(other((f16io ? 4.0 : 8.0) * B * H * (double)W * Cl, st, [&] {
-      if (f16io)
-        return launch_tstp_f16(reinterpret_cast<const uint16_t*>(x), Cl, B, H, W, Cl, nullptr, nullptr,
-                               pooled, st, cur_lens[lvl]);
-      return launch_tstp(x, Cl, B, H, W, Cl, nullptr, nullptr, pooled, st, cur_lens[lvl]);
-    }));
-    if (!two_emb) {
-      WS_LAUNCH(gemm_splitk(conv1d(seg1, pooled, 2 * stats_dim, 0, emb, embed_dim, 0, B, 1, 1, ACT_NONE),
-                            partial, kSplitK, st));
-    } else {            // embed_b = seg_2(seg_bn_1(relu(seg_1(stats))))   (resnet.py:198-202)
-      ConvGemmParams a = conv1d(seg1, pooled, 2 * stats_dim, 0, emb_a, embed_dim, 0, B, 1, 1, ACT_RELU);
-      a.post_scale = arena.at(seg_bn_scale); a.post_shift = arena.at(seg_bn_shift);
-      WS_LAUNCH(gemm_splitk(a, partial, kSplitK, st));
-      WS_LAUNCH(gemm(conv1d(seg2, emb_a, embed_dim, 0, emb, embed_dim, 0, B, 1, 1, ACT_NONE), st));
-    }
-    return end_chunk(tp, true, B, T, emb, st);
+    return pool_and_head(x, Cl, B, H, W, lvl, T, emb, st);
   }
 
-  // the chunk is enqueued: remember what it left; a stopped one (ws_debug_engine_stop_after) returns zeros
-  int end_chunk(BlockTaps& tp, bool full, int B, int T, float* emb, hipStream_t st) {
-    tp.full = full;
-    if (!full)
-      if (int r = stop_chunk(emb, B, st)) return r;
-    block_taps = tp;
-    last_chunk.B = B; last_chunk.T = T; last_chunk.prec = gemm_precision;
-    return 0;
-  }
-
-  int set_stop_after(int n) override {
-    if (n < -1 || n > (int)blocks.size()) {
-      set_error("ws_debug_engine_stop_after: n_blocks = %d, %s has %d residual blocks (-1 = the full forward, 0 = after "
-                "the stem)", n, name.c_str(), (int)blocks.size());
-      return WS_ERR_INVALID_ARG;
-    }
-    stop_after = n;
-    return WS_OK;
-  }
-
-  // ws_debug_engine_tap: what the last chunk's last executed block left in the four rotating buffers ([b][f][t][c] as
-  // rows = B*H*W, cols = C), and the head's tensors after a full forward
+  // ws_debug_engine_tap: what the last chunk's last executed block left in the four rotating buffers and the head's
+  // tensors after a full forward (Cnn2dBase::tap_shared), and 'next_y1': the next block's conv1 output when the block's
+  // conv3 ran fused with it
   int tap(const char* tname, float* dst, int64_t cap_floats, int32_t* rows, int32_t* cols, hipStream_t st) override {
-    if (!last_chunk.B) {
-      set_error("ws_debug_engine_tap: no forward has run on this engine since it was finalized / re-sized");
-      return WS_ERR_INVALID_ARG;
-    }
+    if (int r = tap_guard()) return r;
     const BlockTaps& t = block_taps;
-    const std::string n = tname;
     char why[200];
-    const char* half = "the f16 back-end keeps every activation map in binary16 only";
-    auto map = [&](const float* src, int rows_n, int cols_n) {
-      return tap_copy(tname, t.half ? nullptr : src, t.half ? half : why, rows_n, cols_n, dst, cap_floats, rows, cols, st);
-    };
-    if (n == "stem") {
-      std::snprintf(why, sizeof(why), "the last forward ran %d blocks over the stem's buffer: stop it at 0 "
-                    "(ws_debug_engine_stop_after)", t.n_exec);
-      return map(t.n_exec == 0 ? t.stem : nullptr, t.stem_rows, t.stem_c);
+    if (!std::strcmp(tname, "next_y1")) {
+      if (t.n_exec < 1) std::snprintf(why, sizeof(why), "the last forward was stopped after the stem: no block ran");
+      else std::snprintf(why, sizeof(why), "block %d did not run the fused conv3 + next-conv1 kernel (bneck_c3c1): the "
+                         "next block's conv1 has not run", t.n_exec);
+      return tap_map(tname, t.next_y1, why, t.rows, t.next_c, dst, cap_floats, rows, cols, st);
     }
-    if (n == "block" || n == "mid" || n == "sc" || n == "next_y1") {
-      if (t.n_exec < 1) {
-        std::snprintf(why, sizeof(why), "the last forward was stopped after the stem: no block ran");
-        return map(nullptr, 0, 0);
-      }
-      if (n == "block") return map(t.block, t.rows, t.block_c);
-      if (n == "mid") return map(t.mid, t.rows, t.mid_c);
-      if (n == "sc") {
-        std::snprintf(why, sizeof(why), "block %d has no shortcut convolution", t.n_exec);
-        return map(t.sc, t.rows, t.block_c);
-      }
-      std::snprintf(why, sizeof(why), "block %d did not run the fused conv3 + next-conv1 kernel (bneck_c3c1): the next "
-                    "block's conv1 has not run", t.n_exec);
-      return map(t.next_y1, t.rows, t.next_c);
-    }
-    if (n == "pooled" || n == "emb_a") {
-      std::snprintf(why, sizeof(why), "the last forward was stopped after block %d: pooling and the head did not run",
-                    t.n_exec);
-      if (n == "pooled")
-        return tap_copy(tname, t.full ? pooled : nullptr, why, t.head_rows, 2 * stats_dim, dst, cap_floats, rows, cols, st);
-      return tap_copy(tname, !two_emb ? nullptr : (t.full ? emb_a : nullptr),
-                      two_emb ? why : "the model has one embedding layer (no seg_2)", t.head_rows, embed_dim, dst,
-                      cap_floats, rows, cols, st);
-    }
-    set_error("ws_debug_engine_tap: unknown tensor '%s' (%s: stem, block, mid, sc, next_y1, pooled, emb_a)", tname,
-              name.c_str());
-    return WS_ERR_INVALID_ARG;
+    std::snprintf(why, sizeof(why), "the last forward was stopped after block %d: pooling and the head did not run",
+                  t.n_exec);
+    return tap_shared(tname, dst, cap_floats, rows, cols, st, {"stem, block, mid, sc, next_y1, pooled, emb_a", why});
   }
 
   double flops(int batch, int T) const override {
@@ -393,9 +243,7 @@ struct ResNetModel : ModelBase {
       if (blk.has_sc) macs += (double)Ho * Wo * in * Co;
       H = Ho; W = Wo;
     }
-    macs += 2.0 * stats_dim * embed_dim;
-    if (two_emb) macs += (double)embed_dim * embed_dim;
-    return 2.0 * macs * batch;
+    return 2.0 * (macs + seg_head_macs()) * batch;
   }
 };
 

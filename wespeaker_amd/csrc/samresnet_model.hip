@@ -6,13 +6,14 @@
 //   wespeaker/models/samresnet.py:134-167  SimAM_ResNet34_ASP / SimAM_ResNet100_ASP (front, ASP, bottleneck Linear)
 //   wespeaker/models/pooling_layers.py:151-204 ASP (Conv1d, ReLU, BatchNorm1d, Conv1d, softmax over time)
 //
-// Layout and BN folding as in resnet_model.hip (channels-last [b][f][t][c] fp32, conv -> BN folded on the host).  The
-// SimAM gate needs whole-plane statistics of conv2's output, so conv2 runs without residual / activation and the
-// gate + residual + ReLU is its own kernel (simam_ops.hip).  ASP: the first attention conv reads the last stage as a
-// kh = F', kw = 1 convolution (its K index f*C + c is a host-side permutation of the reference's c*F' + f); the eval
-// BatchNorm1d sits AFTER the ReLU, so it is folded forward into the second conv (W2' = W2 diag(s), b2' = W2 t + b2,
-// float64), whose rows are packed in the same f*C + c order for the pooling kernel.
-#include "model_common.h"
+// Layout, BN folding, the zero-padded activation buffers and the shared taps: cnn2d_base.h (its seg_1 head is not used:
+// the ASP head is this file's).  The SimAM gate needs whole-plane statistics of conv2's output, so conv2 runs without
+// residual / activation and the gate + residual + ReLU is its own kernel (simam_ops.hip).  ASP: the first attention
+// conv reads the last stage as a kh = F', kw = 1 convolution (its K index f*C + c is a host-side permutation of the
+// reference's c*F' + f); the eval BatchNorm1d sits AFTER the ReLU, so it is folded forward into the second conv
+// (W2' = W2 diag(s), b2' = W2 t + b2, float64), whose rows are packed in the same f*C + c order for the pooling
+// kernel.
+#include "cnn2d_base.h"
 
 namespace wsamd {
 
@@ -30,43 +31,27 @@ struct SamBlock {
   int stride = 1, in_planes = 0, planes = 0;
 };
 
-bool starts_with(const std::string& s, const char* p) { return s.compare(0, std::strlen(p), p) == 0; }
-
-struct SamResNetModel : ModelBase {
+struct SamResNetModel : Cnn2dBase {            // (stats_dim = D = C_last * F_last; pooled, partial: the ASP head's)
   SamLayout lay;
   int m = 0;                                 // in_planes, read from front.conv1.weight at finalize
   static constexpr int kHidden = 128;        // ASP hidden width (pooling_layers.py:178)
-  static constexpr int kSplitK = 16;
   static constexpr size_t kTapCap = (size_t)1 << 22;   // floats kept for the 'block1' tap (larger chunks keep none)
-  size_t stem_w = 0, stem_b = 0;
   std::vector<SamBlock> blocks;
   ConvW asp1, asp2, bott;
-  float* buf[4] = {nullptr, nullptr, nullptr, nullptr};
-  size_t act_floats = 0;
-  float *hid = nullptr, *logits = nullptr, *pooled = nullptr, *partial = nullptr;
+  float *hid = nullptr, *logits = nullptr;
   float *sm_part = nullptr, *sm_mu = nullptr, *sm_k = nullptr, *tap_block1 = nullptr;
   bool tap_block1_valid = false;
-  int stats_dim = 0;                         // D = C_last * F_last
 
-  SamResNetModel(const SamLayout& l, int fd, int ed) : ModelBase(l.name, fd, ed), lay(l) {}
+  SamResNetModel(const SamLayout& l, int fd, int ed) : Cnn2dBase(l.name, fd, ed), lay(l) {}
 
   bool wants(const std::string& key) const override {
-    if (key.size() > 20 && key.compare(key.size() - 19, 19, "num_batches_tracked") == 0) return false;
-    static const char* prefixes[] = {"front.conv1.", "front.bn1.", "front.layer1.", "front.layer2.", "front.layer3.",
-                                     "front.layer4.", "pooling.attention.0.", "pooling.attention.2.",
-                                     "pooling.attention.3.", "bottleneck."};
-    for (auto p : prefixes)
-      if (starts_with(key, p)) return true;
-    return false;
+    return wants_prefixes(key, {"front.conv1.", "front.bn1.", "front.layer1.", "front.layer2.", "front.layer3.",
+                                "front.layer4.", "pooling.attention.0.", "pooling.attention.2.", "pooling.attention.3.",
+                                "bottleneck."});
   }
 
   int set_precision(int mode) override {
-    if (mode == 2) {
-      set_error("%s has no binary16-tensor back-end (precision mode 2): its SimAM and ASP kernels are fp32; use "
-                "mode 0 (fp32) or 1 (f16x3)", name.c_str());
-      return WS_ERR_INVALID_ARG;
-    }
-    return ModelBase::set_precision(mode);
+    return mode == 2 ? no_f16io_backend("its SimAM and ASP kernels are") : ModelBase::set_precision(mode);
   }
 
   int finalize(const SD& sd, int max_batch, int max_frames) override {
@@ -86,19 +71,7 @@ struct SamResNetModel : ModelBase {
                 name.c_str(), m);
       return WS_ERR_SHAPE;
     }
-    {   // stem: Conv2d(1, m, 3x3) + bn1 folded -> [C][9] + [C]
-      const HostTensor* wt = get(sd, "front.conv1.weight", {m, 1, 3, 3}, &err);
-      if (!wt) return err;
-      std::vector<double> sc, sh;
-      if ((err = bn_affine(sd, "front.bn1", m, &sc, &sh))) return err;
-      std::vector<float> wf(m * 9), bf(m);
-      for (int c = 0; c < m; ++c) {
-        for (int k = 0; k < 9; ++k) wf[c * 9 + k] = (float)(wt->data[c * 9 + k] * sc[c]);
-        bf[c] = (float)sh[c];
-      }
-      stem_w = arena.add(wf);
-      stem_b = arena.add(bf);
-    }
+    if ((err = pack_stem3x3(sd, "front.conv1", "front.bn1", m, &stem_w, &stem_b))) return err;   // Conv2d(1, m, 3x3) + bn1
     int in_planes = m;
     for (int s = 0; s < 4; ++s) {
       const int planes = m << s;
@@ -118,6 +91,7 @@ struct SamResNetModel : ModelBase {
         blocks.push_back(blk);
       }
     }
+    n_stops = (int)blocks.size();
     const int Fl = feat_dim / 8, Cl = m * 8, D = Cl * Fl;
     stats_dim = D;                                         // pooling_layers.py:169-170
     // attention.0: Conv1d(D -> 128, k = 1) read as a (kh = F', kw = 1) convolution over [b][f][t][c]
@@ -156,34 +130,15 @@ struct SamResNetModel : ModelBase {
     return reserve(max_batch, max_frames);
   }
 
-  static int level_len(int L, int level) {
-    for (int l = 0; l < level; ++l) L = (L - 1) / 2 + 1;
-    return L;
-  }
-
   int reserve(int max_batch, int max_frames) override {
     int err = 0;
-    maxB = max_batch; maxT = max_frames;
-    last_chunk = LastChunk();
-    block_taps = BlockTaps();
+    begin_reserve(max_batch, max_frames);
     tap_block1_valid = false;
     // largest activation: every stage-1 map (F x T x in_planes); later stages halve
     const size_t act = (size_t)maxB * feat_dim * maxT * (size_t)m;
-    if (act >= (size_t)1 << 31) {
-      set_error("%s: max_batch %d x max_frames %d puts %zu elements in one activation map (limit 2^31); "
-                "use a smaller engine chunk", name.c_str(), max_batch, max_frames, act);
-      return WS_ERR_CAPACITY;
-    }
-    if (maxB > 65535) {
-      set_error("%s: max_batch %d exceeds 65535 (one grid row per utterance)", name.c_str(), max_batch);
-      return WS_ERR_CAPACITY;
-    }
-    size_t total = 0;
-    auto take = [&](size_t n) { size_t o = total; total += (n + 63) & ~size_t(63); return o; };
-    size_t ob[4];
-    // (+ 512 zero floats behind every activation buffer: the border taps of the persistent kernel's CONV form)
-    for (int i = 0; i < 4; ++i) ob[i] = take(act + 512);
-    act_floats = act;
+    if ((err = refuse_map_too_large(act)) || (err = refuse_batch_too_large())) return err;
+    Carve cv = begin_carve();
+    for (int i = 0; i < 4; ++i) buf.carve(cv, act);          // the block rotation
     const int Tl = level_len(maxT, 3);
     size_t part = 0;                       // SimAM slice partials: the largest stage
     for (int s = 0, H = feat_dim; s < 4; ++s) {
@@ -192,24 +147,16 @@ struct SamResNetModel : ModelBase {
       const size_t n = (size_t)maxB * simam_slices(H * level_len(maxT, s), C) * 3 * C;
       part = n > part ? n : part;
     }
-    const size_t o_hid = take((size_t)maxB * Tl * kHidden), o_log = take((size_t)maxB * Tl * stats_dim),
-                 o_pool = take((size_t)maxB * 2 * stats_dim), o_part = take((size_t)kSplitK * maxB * embed_dim),
-                 o_sp = take(part), o_mu = take((size_t)maxB * m * 8), o_k = take((size_t)maxB * m * 8),
-                 o_tap = take(act < kTapCap ? act : kTapCap), o_feats = take((size_t)maxB * maxT * feat_dim);
-    if ((err = alloc_workspace(total))) return err;
+    const size_t o_hid = cv.take((size_t)maxB * Tl * kHidden), o_log = cv.take((size_t)maxB * Tl * stats_dim),
+                 o_pool = cv.take((size_t)maxB * 2 * stats_dim), o_part = cv.take((size_t)kSplitK * maxB * embed_dim),
+                 o_sp = cv.take(part), o_mu = cv.take((size_t)maxB * m * 8), o_k = cv.take((size_t)maxB * m * 8),
+                 o_tap = cv.take(act < kTapCap ? act : kTapCap), o_feats = cv.take((size_t)maxB * maxT * feat_dim);
+    if ((err = alloc_workspace(cv.total))) return err;
     float* base = ws.as<float>();
-    for (int i = 0; i < 4; ++i) {
-      buf[i] = base + ob[i];
-      if (hipMemset(buf[i] + act, 0, 512 * sizeof(float)) != hipSuccess) {
-        set_error("zero pad of activation buffer %d", i);
-        return WS_ERR_HIP;
-      }
-    }
     hid = base + o_hid; logits = base + o_log; pooled = base + o_pool; partial = base + o_part;
     sm_part = base + o_sp; sm_mu = base + o_mu; sm_k = base + o_k; tap_block1 = base + o_tap;
     feats_ws = base + o_feats;
-    if (hipDeviceSynchronize() != hipSuccess) return WS_ERR_HIP;
-    return 0;
+    return buf.bind(base);
   }
 
   int min_frames() const override { return 2; }
@@ -230,46 +177,23 @@ struct SamResNetModel : ModelBase {
     return ModelBase::upload_lens(lens_host, batch, frames, st);
   }
 
-  int check_invariants() override {
-    if (!act_floats) return 0;
-    std::vector<float> pad(512);
-    for (int i = 0; i < 4; ++i) {
-      if (hipMemcpy(pad.data(), buf[i] + act_floats, 512 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-        set_error("%s: reading the zero pad of activation buffer %d failed", name.c_str(), i);
-        return WS_ERR_HIP;
-      }
-      for (int k = 0; k < 512; ++k)
-        if (pad[k] != 0.f) {
-          set_error("%s: the zero pad behind activation buffer %d was overwritten (float %d = %g): a kernel stored "
-                    "past its tensor; convolution borders of later forwards are wrong", name.c_str(), i, k, pad[k]);
-          return WS_ERR_STATE;
-        }
-    }
-    return 0;
-  }
-
   int forward_chunk(const float* feats, int B, int T, float* emb, hipStream_t st) override {
-    if (gemm_precision == 2) {               // (set_precision refuses it; never read fp32 buffers as halves)
-      set_error("%s has no binary16-tensor back-end (precision mode 2)", name.c_str());
-      return WS_ERR_STATE;
-    }
+    if (gemm_precision == 2) return no_f16io_backend();      // (set_precision refuses it)
     if (!ragged() && plane_too_small(T)) return refuse_small_plane(T);
-    last_chunk.B = 0;
+    BlockTaps& tp = begin_chunk();             // host-side notes for ws_debug_engine_tap, readable when the chunk ends
     tap_block1_valid = false;
     int H = feat_dim, W = T, lvl = 0;
     float* x = buf[0];
     WS_LAUNCH(other(4.0 * B * H * (double)W * (m + 1), st, [&] {
       return launch_stem_conv3x3_any(feats, B, T, feat_dim, arena.at(stem_w), arena.at(stem_b), m, x, st, cur_lens[0]);
     }));
-    BlockTaps tp;                              // host-side notes for ws_debug_engine_tap, stored when the chunk ends
     tp.n_exec = 0; tp.stem = x; tp.stem_rows = B * H * W; tp.stem_c = m;
-    if (stop_after == 0) return end_chunk(tp, false, B, T, emb, st);
+    if (stop_after == 0) return end_chunk(false, B, T, emb, st);
     auto conv = [&](const ConvW& cw, const float* in, int Cin_, float* out, int Cout_, int Hin_, int Win_, int s_,
                     int pad, int act, int out_lvl) {
       ConvGemmParams p = conv2d(cw, in, Cin_, 0, out, Cout_, 0, B, Hin_, Win_, s_, s_, 1, 1, pad, pad, act);
       p.row_len = cur_lens[out_lvl];                       // stride level of this launch's OUTPUT width
-      for (int i = 0; i < 4; ++i)                          // the zero pad behind the input's buffer
-        if (in == buf[i] && Cin_ <= 512) p.a_zero_off = (long long)act_floats * (long long)sizeof(float);
+      p.a_zero_off = buf.zero_off_for(in, Cin_);           // the zero pad behind the input's buffer
       return gemm(p, st);
     };
     int cur = 0;
@@ -307,7 +231,7 @@ struct SamResNetModel : ModelBase {
         tp.block = x; tp.block_c = P;
         tp.mid = t1; tp.mid_c = P;
         tp.sc = blk.has_sc ? t2 : nullptr;
-        if (stop) return end_chunk(tp, false, B, T, emb, st);
+        if (stop) return end_chunk(false, B, T, emb, st);
       }
     }
     const int Cl = m * 8, D = stats_dim;             // H = F', W = T' here
@@ -324,27 +248,7 @@ struct SamResNetModel : ModelBase {
     }));
     WS_LAUNCH(gemm_splitk(conv1d(bott, pooled, 2 * D, 0, emb, embed_dim, 0, B, 1, 1, ACT_NONE), partial, kSplitK, st));
     tp.head_rows = B * W;                      // rows of hid / logits: the last stage's frames
-    return end_chunk(tp, true, B, T, emb, st);
-  }
-
-  // the chunk is enqueued: remember what it left; a stopped one (ws_debug_engine_stop_after) returns zeros
-  int end_chunk(BlockTaps& tp, bool full, int B, int T, float* emb, hipStream_t st) {
-    tp.full = full;
-    if (!full)
-      if (int r = stop_chunk(emb, B, st)) return r;
-    block_taps = tp;
-    last_chunk.B = B; last_chunk.T = T; last_chunk.prec = gemm_precision;
-    return 0;
-  }
-
-  int set_stop_after(int n) override {
-    if (n < -1 || n > (int)blocks.size()) {
-      set_error("ws_debug_engine_stop_after: n_blocks = %d, %s has %d residual blocks (-1 = the full forward, 0 = after "
-                "the stem)", n, name.c_str(), (int)blocks.size());
-      return WS_ERR_INVALID_ARG;
-    }
-    stop_after = n;
-    return WS_OK;
+    return end_chunk(true, B, T, emb, st);
   }
 
   // ws_debug_engine_tap: 'block1' = the first block's output [b][f][t][c] as (B*F*T, in_planes) -- a copy made
@@ -352,10 +256,7 @@ struct SamResNetModel : ModelBase {
   // ws_debug_engine_stop_after): 'block' = the gated result, 'mid' = conv1's output, 'sc' = the downsample conv's;
   // 'stem' when stopped at 0.  After a full forward: 'hid' (B*T', 128), 'logits' (B*T', D), 'pooled' = the ASP vector
   int tap(const char* tname, float* dst, int64_t cap_floats, int32_t* rows, int32_t* cols, hipStream_t st) override {
-    if (!last_chunk.B) {
-      set_error("ws_debug_engine_tap: no forward has run on this engine since it was finalized / re-sized");
-      return WS_ERR_INVALID_ARG;
-    }
+    if (int r = tap_guard()) return r;
     const int B = last_chunk.B;
     const BlockTaps& t = block_taps;
     const std::string n = tname;
@@ -365,19 +266,6 @@ struct SamResNetModel : ModelBase {
                       t.n_exec == 0 ? "the last forward was stopped after the stem: no block ran"
                                     : "the chunk's stage-1 map exceeds the tap buffer",
                       B * feat_dim * last_chunk.T, m, dst, cap_floats, rows, cols, st);
-    if (n == "stem") {
-      std::snprintf(why, sizeof(why), "the last forward ran %d blocks over the stem's buffer: stop it at 0 "
-                    "(ws_debug_engine_stop_after)", t.n_exec);
-      return tap_copy(tname, t.n_exec == 0 ? t.stem : nullptr, why, t.stem_rows, t.stem_c, dst, cap_floats, rows, cols, st);
-    }
-    if (n == "block" || n == "mid" || n == "sc") {
-      if (t.n_exec < 1)
-        return tap_copy(tname, nullptr, "the last forward was stopped after the stem: no block ran", 0, 0, dst,
-                        cap_floats, rows, cols, st);
-      std::snprintf(why, sizeof(why), "block %d has no downsample convolution", t.n_exec);
-      return tap_copy(tname, n == "block" ? t.block : (n == "mid" ? t.mid : t.sc), why, t.rows, t.block_c, dst,
-                      cap_floats, rows, cols, st);
-    }
     if (n == "hid" || n == "logits" || n == "pooled") {
       std::snprintf(why, sizeof(why), "the last forward was stopped after block %d: the ASP head did not run", t.n_exec);
       if (n == "hid")
@@ -386,9 +274,8 @@ struct SamResNetModel : ModelBase {
         return tap_copy(tname, t.full ? logits : nullptr, why, t.head_rows, stats_dim, dst, cap_floats, rows, cols, st);
       return tap_copy(tname, t.full ? pooled : nullptr, why, B, 2 * stats_dim, dst, cap_floats, rows, cols, st);
     }
-    set_error("ws_debug_engine_tap: unknown tensor '%s' (%s: block1, stem, block, mid, sc, hid, logits, pooled)", tname,
-              name.c_str());
-    return WS_ERR_INVALID_ARG;
+    return tap_shared(tname, dst, cap_floats, rows, cols, st,
+                      {"block1, stem, block, mid, sc, hid, logits, pooled", nullptr, "downsample"});
   }
 
   double flops(int batch, int T) const override {
