@@ -68,9 +68,10 @@ typedef void* ws_stream;                /* hipStream_t */
  * ws_debug_engine_stop_after serves ECAPA-TDNN (1 .. 3) and ws_debug_engine_tap reads its binary16 tensors -- a caller
  * that relied on the refusals sees other results; 111: the ws_spectral_* entries, ws_debug_spectral_dense and
  * ws_debug_spectral_mask added; 112: ws_debug_dwconv3x3 added, ws_engine_create knows the Gemini_DF_ResNet names,
- * ws_debug_engine_tap / ws_debug_engine_stop_after serve them).
+ * ws_debug_engine_tap / ws_debug_engine_stop_after serve them; 113: ws_debug_xi_pool added, ws_engine_create knows
+ * XVEC, XI_VEC_XVEC and the XI_VEC_ECAPA_TDNN names, ws_debug_engine_tap / ws_debug_engine_stop_after serve them).
  * ws_version() returns the library's value: compare it with the header's before calling anything else. */
-#define WS_VERSION 112
+#define WS_VERSION 113
 WS_API int ws_version(void);
 WS_API const char* ws_last_error(void);
 /* Number of fbank frames for num_samples at snip_edges=True (25 ms / 10 ms):
@@ -306,6 +307,22 @@ WS_API int ws_debug_aff_fuse(const float* x, int ldx, int x_off, const float* y,
  * is launched then. */
 WS_API int ws_debug_dwconv3x3(const float* x, float* out, const float* w, const float* bias, int batch, int height,
                               int width, int channels, const int32_t* row_len, ws_stream stream);
+/* XI pooling (wespeaker/models/pooling_layers.py:380-401, stddev=False: the xi-vector's Gaussian posterior inference) as
+ * the engines run it, on caller-supplied DEVICE buffers (tests/test_gpu_tdnn.py).  x and z are fp32 rows
+ * [b * num_frames + t][ldx / ldz >= channels]: the frame tensor and the output of XI's second 1x1 convolution.  Per
+ * utterance b, over the frames [t0_b, t0_b + n_b) with (t0_b, n_b) = windows[2 b], windows[2 b + 1] (HOST int32; NULL:
+ * every utterance's whole num_frames), and per channel d, with sp(v) = v > 20 ? v : log1p(exp(v)):
+ *   lp_t = clamp(2 log(sp(z[t][d])), -15, 15),  m = max(max_t lp_t, prior_logprec[d])
+ *   pooled[b][d] = (sum_t exp(lp_t - m) x[t][d] + exp(prior_logprec[d] - m) prior_mean[d])
+ *                  / (sum_t exp(lp_t - m) + exp(prior_logprec[d] - m))
+ * pooled: [batch][channels] contiguous; prior_mean, prior_logprec: DEVICE float32[channels].  Any channels >= 1 (16-byte
+ * loads when channels, ldx and ldz are multiples of 4 and x, z are 16-byte aligned); 0 <= t0_b, n_b >= 1,
+ * t0_b + n_b <= num_frames; batch <= 65535.  A row's result does not depend on the batch it is in.  Synchronises the
+ * stream when windows are given.  WS_ERR_INVALID_ARG with the reason in ws_last_error for anything outside that
+ * contract; nothing is launched then. */
+WS_API int ws_debug_xi_pool(const float* x, int ldx, const float* z, int ldz, const float* prior_mean,
+                            const float* prior_logprec, float* pooled, int batch, int num_frames, int channels,
+                            const int32_t* windows, ws_stream stream);
 /* Read-only tap on the activations a forward leaves in the engine's workspace (no reference counterpart; the per-layer
  * parity tests of tests/test_gpu_layers.py).  A stream-ordered device-to-device copy of the named fp32 tensor as the
  * LAST chunk of the LAST forward on this engine left it (a batch beyond max_batch runs in chunks: the tap holds the

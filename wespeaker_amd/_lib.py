@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("WS_LIB_PATH") or os.path.join(_HERE, "lib", "libwespe
 
 _lib = None
 
-ABI_VERSION = 112      # = WS_VERSION of include/wespeaker_amd.h
+ABI_VERSION = 113      # = WS_VERSION of include/wespeaker_amd.h
 
 # name -> (restype, argtypes); also used by the ABI test to check every header symbol is exported
 SIGNATURES = {
@@ -64,6 +64,7 @@ SIGNATURES = {
     "ws_debug_dispatch_report": (c_int64, [c_char_p, c_int64]),
     "ws_debug_aff_fuse": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "ws_debug_xi_pool": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ws_debug_dwconv3x3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ws_debug_engine_tap": (c_int, [c_void_p, c_char_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "ws_debug_engine_stop_after": (c_int, [c_void_p, c_int]),

@@ -265,6 +265,7 @@ int ws_engine_create(const char* model_name, int feat_dim, int embed_dim, int de
   if (!m) m = make_samresnet(model_name, feat_dim, embed_dim);
   if (!m) m = make_eres2net(model_name, feat_dim, embed_dim);
   if (!m) m = make_gemini(model_name, feat_dim, embed_dim);
+  if (!m) m = make_tdnn(model_name, feat_dim, embed_dim);
   if (!m) {
     set_error("ws_engine_create: unknown model '%s'", model_name);
     return WS_ERR_UNKNOWN_MODEL;
@@ -751,6 +752,42 @@ int ws_debug_dwconv3x3(const float* x, float* out, const float* w, const float* 
     return WS_ERR_INVALID_ARG;
   }
   WS_HIP_CHECK(launch_dwconv3x3(p, (hipStream_t)stream));
+  return WS_OK;
+}
+
+int ws_debug_xi_pool(const float* x, int ldx, const float* z, int ldz, const float* prior_mean,
+                     const float* prior_logprec, float* pooled, int batch, int num_frames, int channels,
+                     const int32_t* windows, ws_stream stream) {
+  XiPoolParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.x = x; p.ldx = ldx; p.z = z; p.ldz = ldz;
+  p.prior_mean = prior_mean; p.prior_logprec = prior_logprec;
+  p.pooled = pooled; p.ldp = channels;
+  p.B = batch; p.T = num_frames; p.D = channels;
+  const char* why = xi_pool_refusal(p);
+  char msg[96];
+  for (int b = 0; !why && windows && b < batch; ++b) {
+    const long long t0 = windows[2 * b], n = windows[2 * b + 1];
+    if (t0 < 0 || n < 1 || t0 + n > num_frames) {
+      std::snprintf(msg, sizeof(msg), "window %d = (t0 %lld, n %lld) leaves [0, num_frames) or is empty", b, t0, n);
+      why = msg;
+    }
+  }
+  if (why) {                                            // nothing is launched
+    set_error("ws_debug_xi_pool: %s (batch %d, num_frames %d, channels %d)", why, batch, num_frames, channels);
+    return WS_ERR_INVALID_ARG;
+  }
+  if (batch == 0) return WS_OK;
+  hipStream_t st = (hipStream_t)stream;
+  DevBuf win;
+  if (windows) {
+    WS_HIP_CHECK(win.alloc((size_t)batch * 2 * sizeof(int)));
+    WS_HIP_CHECK(hipMemcpyAsync(win.ptr, windows, (size_t)batch * 2 * sizeof(int), hipMemcpyHostToDevice, st));
+    p.win = win.as<int>();
+  }
+  const hipError_t le = launch_xi_pool(p, st);
+  if (windows) (void)hipStreamSynchronize(st);          // the table is freed on return
+  WS_HIP_CHECK(le);
   return WS_OK;
 }
 

@@ -122,14 +122,15 @@ __global__ __launch_bounds__(256) void tstp_kernel(const TX* __restrict__ x, int
                                                    int C, const float* __restrict__ pre_scale,
                                                    const float* __restrict__ pre_shift,
                                                    float* __restrict__ pooled,
-                                                   const int* __restrict__ lens) {
+                                                   const int* __restrict__ lens, int trim) {
   __shared__ float red[4][64];
   const int bf = blockIdx.x, b = bf / F, f = bf - b * F;
   const int cl = threadIdx.x & 63, grp = threadIdx.x >> 6;
   const int c = blockIdx.y * 64 + cl;
   const bool cok = c < C;
-  const TX* base = x + (long long)bf * T * ldx + (cok ? c : 0);
+  const TX* base = x + ((long long)bf * T + trim) * ldx + (cok ? c : 0);
   if (lens) T = lens[b];                      // ragged batch: statistics over the valid columns only
+  T -= 2 * trim;                              // (x-vector: the frames whose receptive field lies inside the utterance)
   float ps = 1.f, pb = 0.f;
   const bool pre = pre_scale != nullptr;
   if (pre && cok) { ps = pre_scale[c]; pb = pre_shift[c]; }
@@ -161,9 +162,10 @@ __global__ __launch_bounds__(256) void tstp_kernel(const TX* __restrict__ x, int
 }
 
 hipError_t launch_tstp(const float* x, int ldx, int B, int F, int T, int C, const float* pre_scale,
-                       const float* pre_shift, float* pooled, hipStream_t stream, const int* lens) {
+                       const float* pre_shift, float* pooled, hipStream_t stream, const int* lens, int trim) {
+  if (trim < 0 || (trim > 0 && F != 1)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(tstp_kernel<float>, dim3(B * F, (C + 63) / 64), dim3(256), 0, stream, x, ldx, F, T,
-                     C, pre_scale, pre_shift, pooled, lens);
+                     C, pre_scale, pre_shift, pooled, lens, trim);
   return hipGetLastError();
 }
 
@@ -171,7 +173,7 @@ hipError_t launch_tstp_f16(const uint16_t* x16, int ldx, int B, int F, int T, in
                            const float* pre_scale, const float* pre_shift, float* pooled,
                            hipStream_t stream, const int* lens) {
   hipLaunchKernelGGL(tstp_kernel<uint16_t>, dim3(B * F, (C + 63) / 64), dim3(256), 0, stream, x16, ldx, F,
-                     T, C, pre_scale, pre_shift, pooled, lens);
+                     T, C, pre_scale, pre_shift, pooled, lens, 0);
   return hipGetLastError();
 }
 

@@ -233,6 +233,7 @@ Model* make_campplus(const std::string& model_name, int feat_dim, int embed_dim)
 Model* make_samresnet(const std::string& model_name, int feat_dim, int embed_dim);
 Model* make_eres2net(const std::string& model_name, int feat_dim, int embed_dim);
 Model* make_gemini(const std::string& model_name, int feat_dim, int embed_dim);
+Model* make_tdnn(const std::string& model_name, int feat_dim, int embed_dim);
 
 }  // namespace wsamd
 

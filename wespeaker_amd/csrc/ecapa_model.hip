@@ -22,6 +22,10 @@ namespace {
 struct EcapaModel : ModelBase {
   int C = 512, w = 64;
   bool glob = false;
+  bool xi = false;              // XI_VEC_ECAPA_TDNN_*: XI posterior pooling instead of ASTP (xi_vector.py:31-44)
+  int xi_hid = 0, pool_dim = 3072;
+  size_t prior_mean = 0, prior_logprec = 0;
+  float* xi_h = nullptr;
   ConvW layer1, blk0[3], res2[3][7], blk2[3], catconv, pool1, pool2, final_lin;
   size_t se_w1[3], se_b1[3], se_w2[3], se_b2[3], se_w2t[3];
   float *out1 = nullptr, *y1 = nullptr, *y2 = nullptr, *y3 = nullptr, *cat = nullptr, *h = nullptr,
@@ -32,6 +36,8 @@ struct EcapaModel : ModelBase {
 
   EcapaModel(const std::string& n, int fd, int ed) : ModelBase(n, fd, ed) {
     glob = n.find("GLOB") != std::string::npos;
+    xi = starts_with(n, "XI_VEC_");
+    pool_dim = xi ? 1536 : 3072;
     C = n.find("c1024") != std::string::npos ? 1024 : 512;
     w = C / 8;
   }
@@ -66,31 +72,36 @@ struct EcapaModel : ModelBase {
       if ((err = add_vec(sd, p + ".3.linear2.bias", C, &se_b2[L]))) return err;
     }
     if ((err = pack_conv1d(sd, "conv", 1536, 3 * C, 1, true, "", "", &catconv))) return err;
+    if (xi) {      // pool1 / pool2 = XI's lin1 / lin2 (lin1_relu_bn.2 folded into lin2)
+      if ((err = pack_xi(sd, "pool", 1536, 1536, &pool1, &pool2, &prior_mean, &prior_logprec, &xi_hid))) return err;
+    } else {
     if ((err = pack_conv1d(sd, "pool.linear1", 128, glob ? 4608 : 1536, 1, true, "", "", &pool1)))
       return err;
     if ((err = pack_conv1d(sd, "pool.linear2", 1536, 128, 1, true, "", "", &pool2))) return err;
-    // bn (3072) -> linear (E x 3072) [-> bn2]: folded in float64
+    }
+    // bn (3072; XI: 1536) -> linear (E x 3072) [-> bn2]: folded in float64
     {
+      const int PK = pool_dim;
       std::vector<double> sc, sh;
-      if ((err = bn_affine(sd, "bn", 3072, &sc, &sh))) return err;
-      const HostTensor* lw = get(sd, "linear.weight", {embed_dim, 3072}, &err);
+      if ((err = bn_affine(sd, "bn", PK, &sc, &sh))) return err;
+      const HostTensor* lw = get(sd, "linear.weight", {embed_dim, PK}, &err);
       if (!lw) return err;
       const HostTensor* lb = get(sd, "linear.bias", {embed_dim}, &err);
       if (!lb) return err;
       std::vector<double> s2(embed_dim, 1.0), t2(embed_dim, 0.0);
       if (sd.count("bn2.running_mean"))
         if ((err = bn_affine(sd, "bn2", embed_dim, &s2, &t2))) return err;
-      std::vector<float> W((size_t)embed_dim * 3072), B(embed_dim);
+      std::vector<float> W((size_t)embed_dim * PK), B(embed_dim);
       for (int o = 0; o < embed_dim; ++o) {
         double acc = lb->data[o];
-        for (int k = 0; k < 3072; ++k) {
-          const double wv = lw->data[(size_t)o * 3072 + k];
+        for (int k = 0; k < PK; ++k) {
+          const double wv = lw->data[(size_t)o * PK + k];
           acc += wv * sh[k];
-          W[(size_t)o * 3072 + k] = (float)(wv * sc[k] * s2[o]);
+          W[(size_t)o * PK + k] = (float)(wv * sc[k] * s2[o]);
         }
         B[o] = (float)(acc * s2[o] + t2[o]);
       }
-      final_lin.N = embed_dim; final_lin.Cin = 3072; final_lin.ldw = 3072;
+      final_lin.N = embed_dim; final_lin.Cin = PK; final_lin.ldw = PK;
       final_lin.w = arena.add(W);
       add_split(&final_lin, W);
       final_lin.b = arena.add(B);
@@ -115,19 +126,30 @@ struct EcapaModel : ModelBase {
            o_part = cv.take((size_t)kSplitK * maxB * (embed_dim > 128 ? embed_dim : 128)),
            o_h16 = cv.take((M * (size_t)(1536 + 3 * C + C + 128 + C + C + 512) + 1) / 2),   // binary16 copies (f16 back-end)
            o_colsum = cv.take(((M + 63) / 64 + 2) * 2 * (C > 1536 ? C : 1536)),
-           o_colsumsq = cv.take(((M + 63) / 64 + 2) * 2 * 1536), o_feats = cv.take(M * feat_dim);
+           o_colsumsq = cv.take(((M + 63) / 64 + 2) * 2 * 1536), o_feats = cv.take(M * feat_dim),
+           o_xih = cv.take(xi ? M * xi_hid : 0);          // (behind everything else: the other names' layout is unchanged)
     if ((err = alloc_workspace(cv.total))) return err;
     float* base = ws.as<float>();
     out1 = base + o_out1; y1 = base + o_y1; y2 = base + o_y2; y3 = base + o_y3; cat = base + o_cat;
     h = base + o_h; att = base + o_att; e = base + o_e; se_s = base + o_s; stats = base + o_stats;
     bias_img = base + o_bias; pooled = base + o_pool; partial = base + o_part;
     colsum = base + o_colsum; colsumsq = base + o_colsumsq; feats_ws = base + o_feats;
+    xi_h = base + o_xih;
     h16 = reinterpret_cast<uint16_t*>(base + o_h16);
     cat16 = h16 + M * 1536; out1_16 = cat16 + M * 3 * C; att16 = out1_16 + M * C; y2_16 = att16 + M * 128; y3_16 = y2_16 + M * C; col16 = y3_16 + M * C;
     return 0;
   }
 
   int min_frames() const override { return 1; }
+
+  int set_precision(int mode) override {
+    if (xi && mode == 2) {
+      set_error("%s has no binary16-tensor back-end (precision mode 2): its XI pooling kernel is fp32; use mode 0 (fp32) "
+                "or 1 (f16x3)", name.c_str());
+      return WS_ERR_INVALID_ARG;
+    }
+    return ModelBase::set_precision(mode);
+  }
 
   int forward_chunk(const float* feats, int B, int T, float* emb, hipStream_t st) override {
     // Ragged chunk (cur_lens set): utterance b owns rows [0, lens[b]) of its T-row slot.  Every conv/linear
@@ -279,6 +301,7 @@ struct EcapaModel : ModelBase {
       pc.row_len = L0;
       WS_LAUNCH(gemm(pc, st));
     }
+    if (xi) return xi_tail(B, T, L0, emb, st);
     // ASTP
     ConvGemmParams a1 = conv1d(pool1, h, 1536, 0, att, 128, 0, B, T, 1, ACT_TANH);
     a1.K = 1536; a1.Cin = 1536;                      // GLOB: only the first 1536 columns multiply h
@@ -348,6 +371,30 @@ struct EcapaModel : ModelBase {
     return 0;
   }
 
+  // XI tail (pooling_layers.py:380-401) in place of ASTP: lin1 -> ReLU [-> BN, folded into lin2] -> lin2 as two GEMMs
+  // (z goes to e, the logits buffer of the unfused ASTP path), XI pooling over the whole utterance, then bn + linear
+  // folded as for ASTP with K = 1536
+  int xi_tail(int B, int T, const int* L0, float* emb, hipStream_t st) {
+    ConvGemmParams a = conv1d(pool1, h, 1536, 0, xi_h, xi_hid, 0, B, T, 1, ACT_RELU);
+    a.row_len = L0;
+    WS_LAUNCH(gemm(a, st));
+    ConvGemmParams z = conv1d(pool2, xi_h, xi_hid, 0, e, 1536, 0, B, T, 1, ACT_NONE);
+    z.row_len = L0;
+    WS_LAUNCH(gemm(z, st));
+    WS_LAUNCH(other(8.0 * B * (double)T * 1536, st, [&] {
+      XiPoolParams q = {};
+      q.x = h; q.ldx = 1536; q.z = e; q.ldz = 1536;
+      q.prior_mean = arena.at(prior_mean); q.prior_logprec = arena.at(prior_logprec);
+      q.pooled = pooled; q.ldp = 1536; q.B = B; q.T = T; q.D = 1536; q.lens = L0; q.trim = 0;
+      return launch_xi_pool(q, st);
+    }));
+    WS_LAUNCH(gemm_splitk(conv1d(final_lin, pooled, 1536, 0, emb, embed_dim, 0, B, 1, 1, ACT_NONE), partial, kSplitK, st));
+    last_chunk.B = B; last_chunk.T = T; last_chunk.prec = gemm_precision;
+    last_chunk.chain_half = false; last_chunk.y2_half = false; last_chunk.f16io = false; last_chunk.col16 = false;
+    last_chunk.att = false; last_chunk.blocks = 3; last_chunk.full = true;
+    return 0;
+  }
+
   // a chunk stopped after SE-Res2 block n (1 .. 3): what the taps may read, and a zero embedding
   int end_stopped(int n, int B, int T, bool f16io, bool allf16, bool col16_used, float* emb, hipStream_t st) {
     if (int r = stop_chunk(emb, B, st)) return r;
@@ -398,18 +445,23 @@ struct EcapaModel : ModelBase {
                                         "only the f16 back-end with T >= 64 stores conv3's output in binary16", M, C, dst,
                                         cap_floats, rows, cols, st);
     if (!full) {
-      static const char* tail[] = {"h", "h16", "att", "att16", "stats", "bias_img", "pooled"};
+      static const char* tail[] = {"h", "h16", "att", "att16", "stats", "bias_img", "pooled", "xi_hid", "xi_z"};
       for (auto t : tail)
         if (n == t) return tap_copy(name, nullptr, stopped, 0, 0, dst, cap_floats, rows, cols, st);
     }
     if (n == "h") return tap_copy(name, lc.chain_half ? nullptr : h, half, M, 1536, dst, cap_floats, rows, cols, st);
     if (n == "h16") return tap_copy16(name, lc.f16io ? h16 : nullptr, nof16, M, 1536, dst, cap_floats, rows, cols, st);
-    if (n == "att") return tap_copy(name, lc.att ? att : nullptr, "astp_fused_kernel keeps linear1's output on the chip",
+    if (n == "att") return tap_copy(name, lc.att ? att : nullptr,
+                                    xi ? "XI pooling has no attention bottleneck: read xi_hid"
+                                       : "astp_fused_kernel keeps linear1's output on the chip",
                                     M, 128, dst, cap_floats, rows, cols, st);
     if (n == "att16") return tap_copy16(name, lc.f16io ? att16 : nullptr, nof16, M, 128, dst, cap_floats, rows, cols, st);
     if (n == "stats") return tap_copy(name, glob ? stats : nullptr, noglob, lc.B, 3072, dst, cap_floats, rows, cols, st);
     if (n == "bias_img") return tap_copy(name, glob ? bias_img : nullptr, noglob, lc.B, 128, dst, cap_floats, rows, cols, st);
-    if (n == "pooled") return tap_copy(name, pooled, "", lc.B, 3072, dst, cap_floats, rows, cols, st);
+    if (n == "pooled") return tap_copy(name, pooled, "", lc.B, pool_dim, dst, cap_floats, rows, cols, st);
+    const char* noxi = "only the XI_VEC_ECAPA_TDNN models have the XI log-precision estimator";
+    if (n == "xi_hid") return tap_copy(name, xi ? xi_h : nullptr, noxi, M, xi_hid, dst, cap_floats, rows, cols, st);
+    if (n == "xi_z") return tap_copy(name, xi ? e : nullptr, noxi, M, 1536, dst, cap_floats, rows, cols, st);
     set_error("ws_debug_engine_tap: unknown tensor '%s' (out1, cat, h, att, y1, y2, y3, se_s, stats, bias_img, pooled; "
               "binary16: col16, out1_16, cat16, h16, att16, y2_16, y3_16)", name);
     return WS_ERR_INVALID_ARG;
@@ -419,11 +471,11 @@ struct EcapaModel : ModelBase {
     macs += (double)feat_dim * 5 * C;                       // layer1
     macs += 3.0 * (2.0 * C * C + 7.0 * w * w * 3);          // blocks (per frame)
     macs += 3.0 * C * 1536;                                 // cat conv
-    macs += 1536.0 * 128 * 2;                               // ASTP linear1 (h part) + linear2
+    macs += 1536.0 * (xi ? xi_hid : 128) * 2;               // ASTP linear1 (h part) + linear2; XI: lin1 + lin2
     double per_utt = macs * T;
     per_utt += 3.0 * (2.0 * C * 128);                       // SE FCs
     if (glob) per_utt += 128.0 * 3072;                      // ASTP context columns (folded to a bias)
-    per_utt += 3072.0 * embed_dim;                          // final linear
+    per_utt += (double)pool_dim * embed_dim;                // final linear
     return 2.0 * per_utt * batch;
   }
 };
@@ -432,7 +484,7 @@ struct EcapaModel : ModelBase {
 
 Model* make_ecapa(const std::string& model_name, int feat_dim, int embed_dim) {
   static const char* names[] = {"ECAPA_TDNN_c512", "ECAPA_TDNN_GLOB_c512", "ECAPA_TDNN_c1024",
-                                "ECAPA_TDNN_GLOB_c1024"};
+                                "ECAPA_TDNN_GLOB_c1024", "XI_VEC_ECAPA_TDNN_c512", "XI_VEC_ECAPA_TDNN_c1024"};
   for (auto n : names)
     if (model_name == n) return new EcapaModel(model_name, feat_dim, embed_dim);
   return nullptr;

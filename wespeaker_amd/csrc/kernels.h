@@ -258,8 +258,10 @@ hipError_t launch_stem_conv3x3(const float* feats, int B, int T, int F, const fl
 // TSTP (pooling_layers.py:78-85) over channels-last x[(b*F + f)*T + t][c]: mean and
 // sqrt(unbiased var + 1e-7) over t; optional pre-activation relu(x*pre_scale[c] + pre_shift[c])
 // (CAM++ out_nonlinear).  pooled[b][c*F + f] = mean, pooled[b][C*F + c*F + f] = std.
+// trim (F == 1): the statistics run over the frames [trim, len - trim) of every utterance (the x-vector's frame window)
 hipError_t launch_tstp(const float* x, int ldx, int B, int F, int T, int C, const float* pre_scale,
-                       const float* pre_shift, float* pooled, hipStream_t stream, const int* lens = nullptr);
+                       const float* pre_shift, float* pooled, hipStream_t stream, const int* lens = nullptr,
+                       int trim = 0);
 hipError_t launch_tstp_f16(const uint16_t* x16, int ldx, int B, int F, int T, int C,
                            const float* pre_scale, const float* pre_shift, float* pooled,
                            hipStream_t stream, const int* lens = nullptr);
@@ -280,6 +282,24 @@ hipError_t launch_simam_residual_relu(const float* y, const float* res, int ldr,
 // (variance clamped at 1e-5) of x[(b*F + f)*T + t][c] -> pooled[b] = [mean(D) | std(D)], D index c*F + f
 hipError_t launch_asp_pool(const float* x, const float* e, int B, int F, int T, int C, float* pooled,
                            hipStream_t stream, const int* lens = nullptr);
+// ---- xi-vector (xi_pool.hip)
+// XI pooling (pooling_layers.py:380-401, stddev=False): per (utterance, channel) a softmax over the frames of a window
+// PLUS one prior pseudo-frame of the clamped log-precisions lp = clamp(2 log softplus(z), -15, 15), and the mean of x
+// (and prior_mean) under those weights -> pooled[b][d].  x, z: fp32 rows [b*T + t][ld >= D]; the window of utterance b
+// is win[2b], win[2b + 1] = (t0, n) (device array) or, without win, [trim, len_b - trim) with len_b = lens[b] or T;
+// whoever launches it guarantees 0 <= t0, n >= 1, t0 + n <= T.  Any D; 16-byte loads when D, ldx, ldz are multiples of
+// 4 and the pointers are aligned.  One pass over x and z; a row's bits do not depend on its batch.
+struct XiPoolParams {
+  const float* x; int ldx;
+  const float* z; int ldz;
+  const float* prior_mean; const float* prior_logprec;
+  float* pooled; int ldp;
+  int B, T, D;
+  const int* lens; int trim;
+  const int* win;
+};
+const char* xi_pool_refusal(const XiPoolParams& p);        // what the launcher objects to (null: nothing)
+hipError_t launch_xi_pool(const XiPoolParams& p, hipStream_t stream);
 // ---- ERes2Net (aff_fuse.hip)
 // Attentional feature fusion (eres2net.py:75-103) in one launch over channels-last rows (fp32, exact-fp32 MFMA):
 //   h = silu(W1 [x[m] | y[m]] + b1),  a = 1 + tanh(W2 h + b2),  out[m] = x[m] * a + y[m] * (2 - a)

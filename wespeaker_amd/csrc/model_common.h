@@ -434,6 +434,71 @@ struct ModelBase : Model {
     return 0;
   }
 
+  // A layer whose weights the family has already worked out in float64 (a fold pack_conv has no form for, or an output
+  // width padded for the kernels): W(n, tap, ci) and bias(n) for n < N, rows [N, Npad) all zero -- those output
+  // channels come out as act(0) = 0.  post_scale / post_shift (empty: none) are padded with zeros as well.
+  void pack_dense(int N, int Npad, int Cin, int k, const std::function<double(int, int, int)>& W,
+                  const std::function<double(int)>& bias, const std::vector<double>& post_scale,
+                  const std::vector<double>& post_shift, ConvW* out) {
+    out->N = Npad; out->Cin = Cin; out->kh = 1; out->kw = k;
+    out->ldw = round_up(Cin * k, 64);
+    std::vector<float> packed((size_t)Npad * out->ldw, 0.f), b(Npad, 0.f);
+    for (int n = 0; n < N; ++n) {
+      for (int tp = 0; tp < k; ++tp)
+        for (int ci = 0; ci < Cin; ++ci) packed[(size_t)n * out->ldw + (size_t)tp * Cin + ci] = (float)W(n, tp, ci);
+      b[n] = (float)bias(n);
+    }
+    out->w = arena.add(packed);
+    add_split(out, packed);
+    out->b = arena.add(b);
+    out->has_b = true;
+    if (!post_scale.empty()) {
+      std::vector<float> f(Npad, 0.f), g(Npad, 0.f);
+      for (int n = 0; n < N; ++n) { f[n] = (float)post_scale[n]; g[n] = (float)post_shift[n]; }
+      out->scale = arena.add(f);
+      out->shift = arena.add(g);
+      out->has_post = true;
+    }
+  }
+
+  // XI pooling's log-precision estimator (pooling_layers.py:361-367) under `prefix`: lin1 = Conv1d(D -> H, k1) + ReLU
+  // (the engine runs it with ACT_RELU), then BatchNorm1d(H) folded in float64 into lin2 = Conv1d(H -> D, k1) -- exact,
+  // a 1x1 convolution follows the BN: W2' = W2 diag(s), b2' = b2 + W2 t.  lin2's output width is padded to Dpad.
+  int pack_xi(const SD& sd, const std::string& prefix, int D, int Dpad, ConvW* lin1, ConvW* lin2, size_t* prior_mean,
+              size_t* prior_logprec, int* hidden) {
+    int err = 0;
+    auto it = sd.find(prefix + ".lin1_relu_bn.0.weight");
+    if (it == sd.end() || it->second.shape.size() != 3) {
+      set_error("missing tensor '%s.lin1_relu_bn.0.weight' for model %s", prefix.c_str(), name.c_str());
+      return WS_ERR_MISSING_TENSOR;
+    }
+    const int H = (int)it->second.shape[0];
+    *hidden = H;
+    if (H <= 0 || (H & 3)) {
+      set_error("%s: XI's hidden size %d must be a positive multiple of 4", name.c_str(), H);
+      return WS_ERR_SHAPE;
+    }
+    if ((err = pack_conv1d(sd, prefix + ".lin1_relu_bn.0", H, D, 1, true, "", "", lin1))) return err;
+    std::vector<double> sc, sh;
+    if ((err = bn_affine(sd, prefix + ".lin1_relu_bn.2", H, &sc, &sh))) return err;
+    const HostTensor* w2 = get(sd, prefix + ".lin2.weight", {D, H, 1}, &err);
+    if (!w2) return err;
+    const HostTensor* b2 = get(sd, prefix + ".lin2.bias", {D}, &err);
+    if (!b2) return err;
+    pack_dense(D, Dpad, H, 1, [&](int n, int, int ci) { return (double)w2->data[(size_t)n * H + ci] * sc[ci]; },
+               [&](int n) {
+                 double acc = b2->data[n];
+                 for (int k = 0; k < H; ++k) acc += (double)w2->data[(size_t)n * H + k] * sh[k];
+                 return acc;
+               }, {}, {}, lin2);
+    const HostTensor* t;
+    if (!(t = get(sd, prefix + ".prior_mean", {1, D}, &err))) return err;
+    *prior_mean = arena.add(t->data);
+    if (!(t = get(sd, prefix + ".prior_logprec", {1, D}, &err))) return err;
+    *prior_logprec = arena.add(t->data);
+    return 0;
+  }
+
   // Conv1d weight (N, Cin, k) -> [n][tap*Cin + ci]
   int pack_conv1d(const SD& sd, const std::string& prefix, int N, int Cin, int k, bool has_bias,
                   const std::string& fold_bn, const std::string& post_bn, ConvW* out) {

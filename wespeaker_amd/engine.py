@@ -23,9 +23,21 @@ SUPPORTED_MODELS = ("ECAPA_TDNN_c512", "ECAPA_TDNN_GLOB_c512", "ECAPA_TDNN_c1024
                     "ECAPA_TDNN_GLOB_c1024", "ResNet18", "ResNet34", "ResNet50", "ResNet101",
                     "ResNet152", "ResNet221", "ResNet293", "CAMPPlus", "SimAM_ResNet34_ASP", "SimAM_ResNet100_ASP",
                     "ERes2Net34_Base", "ERes2Net34_Large", "ERes2Net34_aug", "Gemini_DF_ResNet60", "Gemini_DF_ResNet114",
-                    "Gemini_DF_ResNet183", "Gemini_DF_ResNet237")
+                    "Gemini_DF_ResNet183", "Gemini_DF_ResNet237", "XVEC", "XI_VEC_XVEC", "XI_VEC_ECAPA_TDNN_c512",
+                    "XI_VEC_ECAPA_TDNN_c1024")
 
-DEFAULT_EMBED_DIM = {"ECAPA": 192, "ResNe": 256, "CAMPP": 512, "SimAM": 256, "ERes2": 512, "Gemin": 256}
+DEFAULT_EMBED_DIM = {"ECAPA": 192, "ResNe": 256, "CAMPP": 512, "SimAM": 256, "ERes2": 512, "Gemin": 256, "XVEC": 512,
+                     "XI_VE": 512}
+
+
+def check_pooling_func(model_name, pooling):
+    """The x-vector family's `pooling_func` (tdnn.py:64, xi_vector.py:31-49): XVEC pools with TSTP, the XI_VEC_* names with
+    XI -- the one pooling layer each engine has.  Anything else raises NotImplementedError; other families are not this
+    function's business."""
+    if model_name == "XVEC" and pooling not in (None, "TSTP"):
+        raise NotImplementedError("%s with pooling_func=%r (only TSTP)" % (model_name, pooling))
+    if model_name.startswith("XI_VEC_") and pooling not in (None, "XI"):
+        raise NotImplementedError("%s with pooling_func=%r (only XI)" % (model_name, pooling))
 
 
 def simam_model_args(state_dict, feat_dim, model_args):
@@ -291,6 +303,11 @@ class NativeSpeakerModel:
     # stem (stopped at 0); ds (the last executed stop point is a downsample layer) or exp / dw / block (it is a block:
     # conv1's output and the depthwise kernel's, 4 dim channels, and the block's output); pooled / emb_a after a full forward
     GEMINI_TAP_NAMES = ("stem", "ds", "exp", "dw", "block", "pooled", "emb_a")
+    # XVEC / XI_VEC_XVEC: stop_after counts the TDNN layers (1 .. 5); frame = the last executed layer after its BN,
+    # (B * T_slot, hid_dim or stats_dim) -- every layer is T rows long, the reference's valid frames of layer k are the
+    # rows [r_k, len - r_k), r = 2, 4, 7, 7, 7; pooled / emb_a after a full forward, xi_hid / xi_z (XI's lin1 and lin2
+    # outputs; also XI_VEC_ECAPA_TDNN_*) with XI pooling
+    TDNN_TAP_NAMES = ("frame", "pooled", "emb_a", "xi_hid", "xi_z")
 
     def stop_after(self, n_blocks):
         """Diagnostic (ResNet / SimAM-ResNet / ERes2Net / Gemini DF-ResNet / CAMPPlus / ECAPA-TDNN;

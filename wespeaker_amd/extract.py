@@ -758,6 +758,8 @@ def build_gpu_extractor(configs, model_path, device=None, max_batch=256, max_fra
     pooling = margs.pop("pooling_func", None)
     if configs["model"].startswith(("ERes2Net", "Gemini_DF_ResNet")) and pooling not in (None, "TSTP"):      # eres2net.py:326: any pooling layer;
         raise NotImplementedError("%s with pooling_func=%r (only TSTP)" % (configs["model"], pooling))   # the engine has TSTP
+    from .engine import check_pooling_func
+    check_pooling_func(configs["model"], pooling)         # XVEC: TSTP; XI_VEC_*: XI
     feat_dim = int(margs.pop("feat_dim", fc["num_mel_bins"]))
     embed_dim = margs.pop("embed_dim", None)
     sd = _load_state_dict(model_path)

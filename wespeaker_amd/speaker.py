@@ -17,7 +17,7 @@ import yaml
 
 from . import _lib
 from .audio import load_wav
-from .engine import Frontend, NativeSpeakerModel, default_device
+from .engine import Frontend, NativeSpeakerModel, check_pooling_func, default_device
 
 
 def _load_state_dict(path: str):
@@ -49,6 +49,7 @@ def load_model_pt(model_name_or_path: str, device=None, max_batch=64, max_frames
         raise NotImplementedError("ECAPA-TDNN with pooling_func=%r (only ASTP)" % pooling)
     if config["model"].startswith(("ResNet", "CAMPPlus", "ERes2Net", "Gemini_DF_ResNet")) and pooling not in (None, "TSTP"):
         raise NotImplementedError("%s with pooling_func=%r (only TSTP)" % (config["model"], pooling))
+    check_pooling_func(config["model"], pooling)          # XVEC: TSTP; XI_VEC_*: XI
     sd = _load_state_dict(os.path.join(model_dir, "avg_model.pt"))
     if model_args.pop("emb_bn", False) and "bn2.running_mean" not in sd:
         raise KeyError("emb_bn=True but bn2.* is missing from the checkpoint")
